@@ -12,8 +12,15 @@ One timed "step" = `step()` for every env (ego + actors + raster + collision/rew
 terminated (reset_mask = terminated | truncated, served on the device from a
 pre-built scene bank). Inputs are resident in HBM before the timed region.
 `value` = env-steps/s summed over ranks (weak scaling: envs per GPU fixed).
-The wire-format observation (float32 one-hot 4-stack / gray stack) is timed
-in a second pass and reported as `with_wire_obs`.
+
+A plain run does what that figure needs and no more: it builds the scenes,
+warms up, times one pass of exactly `--steps` steps, writes the last step's
+outputs if `--dump-outputs DIR` is given, and prints the result line.
+`--full` adds everything else: five timed passes (value = their median), the
+per-kernel and roofline figures, the wire-format observation (float32 one-hot
+4-stack / gray stack, timed in a pass of its own and reported as
+`with_wire_obs`), the fresh-scene pass, the reference-surface loops and the
+CPU baseline.
 """
 from __future__ import annotations
 
@@ -411,11 +418,66 @@ def surface_loop(cfgd, n, device, acts, pool, steps, warmup, fresh):
     return out
 
 
+def warm_clocks(warm_env, acts, seconds=0.5):
+    """Bring the GPU to its steady clocks right before the timed passes (a fresh
+    box's first few ms of kernels, and the first after an idle spell, run
+    measurably slower): the canonical loop for `seconds` of wall time on
+    `warm_env`, a second env of the same workload. How many steps fit into that
+    time differs from run to run, and every reset advances the device's per-env
+    reset counts (which pick the bank rows of later resets), so the measured
+    env never runs this loop: its outputs are the same in every run."""
+    import torch
+    t_end = time.perf_counter() + seconds
+    while time.perf_counter() < t_end:
+        for t in range(min(20, acts.shape[0])):
+            warm_env.step_async_only(acts[t])
+            warm_env.step_infos()
+            warm_env.reset_terminated()
+        torch.cuda.synchronize()
+
+
+DUMP_FRAME_BYTES = 32 << 20  # float32 bytes of the sampled frames (the whole dump stays far below 64 MB)
+
+
+def dump_outputs(env, out_dir):
+    """What the caller of the timed path holds after its last step (step +
+    canonical reset): the newest frames, rewards, flags, causes and the comfort
+    export, as float32 / float64 .npy files. The frames of a fixed seeded sample
+    of envs are written whole; `frames_sum` covers every env."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n, S = env.num_envs, env.S
+    frames = env.frames()
+    k = max(1, min(n, DUMP_FRAME_BYTES // (4 * S * S)))
+    ids = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    sel = torch.from_numpy(ids).to(frames.device)
+    arrays = {
+        "frames": frames[sel].cpu().numpy().astype(np.float32),
+        "frames_env_ids": ids.astype(np.float64),
+        "frames_sum": frames.reshape(n, -1).sum(dim=1, dtype=torch.float64).cpu().numpy(),
+        "reward": env.reward.cpu().numpy().astype(np.float64),
+        "terminated": env.term.cpu().numpy().astype(np.float32),
+        "truncated": env.trunc.cpu().numpy().astype(np.float32),
+        "cause": env.cause.cpu().numpy().astype(np.float32),
+        "comfort": env.info.cpu().numpy().astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: five timed passes (median), per-kernel "
+                         "and roofline figures, the wire observation, fresh-scene resets, the reference-surface loops "
+                         "and the CPU baseline (the options below that switch these off or size them apply here)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (frames of a fixed sample of envs, rewards, flags, "
+                         "causes, comfort export) as DIR/<name>.npy; identical from run to run with the same arguments")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (default: the config's)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -428,8 +490,9 @@ def main():
                     help="host processes feeding fresh seeded scenes into the reset bank in a last timed pass (0: off)")
     ap.add_argument("--burn-in", type=int, default=200,
                     help="canonical-loop steps before the timed passes, which all start from the state they leave")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed passes of exactly --steps steps each (re-seeded between); value = their median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed passes of exactly --steps steps each (re-seeded between); value = their median "
+                         "(default: 1, with --full 5)")
     ap.add_argument("--no-defer-reset", action="store_true",
                     help="launch every canonical reset at once (k_reset_mask) instead of folding it into the next step")
     ap.add_argument("--surface-steps", type=int, default=None,
@@ -442,6 +505,13 @@ def main():
                     help="full (default, as the reference's step() always runs Stats.step, carlabev.py:226-227): "
                          "device episode statistics + a StepInfos per step (not read); none: statistics off")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:  # a plain run: the headline pass only
+        args.no_wire = args.no_cpu_baseline = True
+        args.fresh_workers = args.surface_steps = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -475,6 +545,7 @@ def main():
     from carlabev_env_amd._lib import check, lib
     env, host_recs, start_recs = build_env(cfgd, n, rank, device, args.info_mode, scenes,
                                            defer_reset=not args.no_defer_reset)
+    warm_env, _, _ = build_env(cfgd, n, rank, device, args.info_mode, scenes, defer_reset=not args.no_defer_reset)
     del scenes
     P = env.params
     total_steps = args.warmup + args.steps
@@ -564,50 +635,48 @@ def main():
     # stream carry implicit synchronisation that costs several us per kernel.
     stream = torch.cuda.Stream(device)
     with torch.cuda.stream(stream):
-        # bring the GPU to its steady clocks before any timed pass (a fresh box's first
-        # few ms of kernels run measurably slower); the state is re-seeded afterwards
-        t_end = time.perf_counter() + 0.5
-        while time.perf_counter() < t_end:
-            for t in range(min(20, total_steps)):
-                one_step(t, False)
-            torch.cuda.synchronize()
         burn_resets = burn_in() if burn else 0
         passes = []
         term0 = env.termination_count()
         rows0 = env.bank_rows_used()
         counts0 = env.reset_counts()
+        warm_clocks(warm_env, acts)
         for _ in range(max(1, args.repeats)):  # headline passes, no instrumentation
             reseed()
             passes.append(timed(False, False))
+        log(f"[rank {rank}] ms per step of the timed passes, in order: "
+            + ", ".join(f"{p[0] / args.steps * 1e3:.4f}" for p in passes))
+        dumped = None
+        if args.dump_outputs and rank == 0:  # the last headline pass's last step, before anything else runs
+            dumped = dump_outputs(env, args.dump_outputs)
         pass_resets = env.termination_count() - term0
         pass_rows = env.bank_rows_used() - rows0
         distinct_rows = int(np.unique(env.bank_rows_between(counts0, env.reset_counts(), env.bank.shape[0])).size)
         els = sorted(p[0] for p in passes)
         el = els[len(els) // 2]
         host_enq = sorted(p[2] for p in passes)[len(els) // 2]
-        peak = measure_peaks(env, device)
-        reseed()
-        el_prof, ms3, _ = timed(False, True)  # same workload with HIP events around each kernel (roofline)
         value = world * n * args.steps / el
-        burst_ms = None
-        # k_raster's own launch duration: one more step (no reset, so every
-        # record holds this step's render set-up), then a burst of raster
-        # launches over it between two events (cbev_profile_raster); the
-        # per-kernel events above also count each launch's dispatch gap
-        env.step_async_only(acts[total_steps - 1])
-        bm = ctypes.c_double()
-        check(lib().cbev_profile_raster(env._ctx, env.records.data_ptr(), n, env.frames().data_ptr(),
-                                        args.raster_reps, env._stream(), ctypes.byref(bm)), "profile_raster")
-        burst_ms = bm.value
-        wire_value = None
-        if not args.no_wire:
+        peak = el_prof = ms3 = burst_ms = wire_value = fresh = None
+        if args.full:
+            peak = measure_peaks(env, device)
             reseed()
-            el_w, _, _ = timed(True, False)
-            wire_value = world * n * args.steps / el_w
-        fresh = None
-        if pool is not None:
-            reseed()
-            fresh = fresh_pass(env, pool, one_step, args, world, n, device)
+            el_prof, ms3, _ = timed(False, True)  # same workload with HIP events around each kernel (roofline)
+            # k_raster's own launch duration: one more step (no reset, so every
+            # record holds this step's render set-up), then a burst of raster
+            # launches over it between two events (cbev_profile_raster); the
+            # per-kernel events above also count each launch's dispatch gap
+            env.step_async_only(acts[total_steps - 1])
+            bm = ctypes.c_double()
+            check(lib().cbev_profile_raster(env._ctx, env.records.data_ptr(), n, env.frames().data_ptr(),
+                                            args.raster_reps, env._stream(), ctypes.byref(bm)), "profile_raster")
+            burst_ms = bm.value
+            if not args.no_wire:
+                reseed()
+                el_w, _, _ = timed(True, False)
+                wire_value = world * n * args.steps / el_w
+            if pool is not None:
+                reseed()
+                fresh = fresh_pass(env, pool, one_step, args, world, n, device)
     surf = surf_fresh = None
     if args.surface_steps > 0:
         surf = surface_loop(cfgd, n, device, acts_all, bpool, args.surface_steps, args.surface_warmup, fresh=False)
@@ -615,27 +684,51 @@ def main():
                                   fresh=True)
 
     S = P.size
-    # per env: S^2 texels sampled + S^2 frame bytes + ego state
-    algo_bytes = 2 * S * S + 64
-    raster_ms = burst_ms if burst_ms is not None else ms3[2]
-    achieved = n * algo_bytes / (raster_ms * 1e-3) / 1e9
-    traffic = write_bytes = None
-    pmc_path = os.path.join(REPO, "profiles", f"pmc_raster_config{args.config}.json")
-    if os.path.exists(pmc_path):
-        with open(pmc_path) as f:
-            pmc = json.load(f)
-        if pmc.get("envs") == n:
-            traffic = pmc.get("hbm_bytes_per_launch")
-            write_bytes = pmc.get("write_kb", 0.0) * 1024
-    t_s = raster_ms * 1e-3
-    frame_bytes = n * S * S
-    counter_fields = {
-        # counter-measured DRAM rates of the same launch time (profiles/pmc_raster_config*.json)
-        "write_frac_measured": None if write_bytes is None else round(write_bytes / t_s / 1e9 / peak["write_gbs"], 4),
-        "hbm_counter_frac": None if traffic is None else round(traffic / t_s / 1e9 / HBM_PEAK_GBS, 4),
-        # kernel time over the time this box's fill_ needs for the frame bytes alone
-        "write_floor_ratio": round(t_s / (frame_bytes / (peak["write_gbs"] * 1e9)), 3),
-    }
+    full_fields = {}
+    if args.full and rank == 0:
+        # per env: S^2 texels sampled + S^2 frame bytes + ego state
+        algo_bytes = 2 * S * S + 64
+        raster_ms = burst_ms if burst_ms is not None else ms3[2]
+        achieved = n * algo_bytes / (raster_ms * 1e-3) / 1e9
+        traffic = write_bytes = None
+        pmc_path = os.path.join(REPO, "profiles", f"pmc_raster_config{args.config}.json")
+        if os.path.exists(pmc_path):
+            with open(pmc_path) as f:
+                pmc = json.load(f)
+            if pmc.get("envs") == n:
+                traffic = pmc.get("hbm_bytes_per_launch")
+                write_bytes = pmc.get("write_kb", 0.0) * 1024
+        t_s = raster_ms * 1e-3
+        frame_bytes = n * S * S
+        counter_fields = {
+            # counter-measured DRAM rates of the same launch time (profiles/pmc_raster_config*.json)
+            "write_frac_measured": (None if write_bytes is None
+                                    else round(write_bytes / t_s / 1e9 / peak["write_gbs"], 4)),
+            "hbm_counter_frac": None if traffic is None else round(traffic / t_s / 1e9 / HBM_PEAK_GBS, 4),
+            # kernel time over the time this box's fill_ needs for the frame bytes alone
+            "write_floor_ratio": round(t_s / (frame_bytes / (peak["write_gbs"] * 1e9)), 3),
+        }
+        full_fields = {
+            "ms_per_step_with_kernel_events": round(el_prof / args.steps * 1e3, 4),
+            # per-step HIP-event spans; with no actor slots (config 2) k_actors is not launched and
+            # its span is only the two back-to-back event records
+            "kernel_ms": {"k_actors": (round(ms3[0], 5) if cfgd["caps"]["actor_cap"] > 0 else None),
+                          "k_ego": round(ms3[1], 5), "k_raster": round(ms3[2], 5)},
+            "raster_ms_per_launch": None if burst_ms is None else round(burst_ms, 5),
+            "roofline": {"bound": "hbm", "kernel": "k_raster", "achieved": round(achieved, 1),
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                         "peak_measured": peak, **counter_fields,
+                         "traffic": traffic, "algorithmic_bytes_per_env": algo_bytes,
+                         "timing": (f"HIP events around {args.raster_reps} back-to-back launches on the step stream"
+                                    if burst_ms is not None else "HIP events around each launch in the timed steps"),
+                         # the same bytes over the per-step event time (includes each launch's dispatch gap)
+                         "achieved_step_events": round(n * algo_bytes / (ms3[2] * 1e-3) / 1e9, 1)},
+            "with_wire_obs": None if wire_value is None else round(wire_value, 1),
+            "fresh_resets": fresh,
+            # the reference surface's own loop (INTEGRATION.md §1), host scene builds included
+            "surface_loop": surf,
+            "surface_loop_fresh": surf_fresh,
+        }
     cpu = None
     if rank == 0 and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(cfgd, host_recs, env, args.cpu_seconds)
@@ -676,30 +769,15 @@ def main():
             "bank_rows_handed_out": pass_rows,
             "distinct_bank_rows_handed_out": distinct_rows,
             "host_enqueue_ms_per_step": round(host_enq / args.steps * 1e3, 4),
-            "ms_per_step_with_kernel_events": round(el_prof / args.steps * 1e3, 4),
-            # per-step HIP-event spans; with no actor slots (config 2) k_actors is not launched and
-            # its span is only the two back-to-back event records
-            "kernel_ms": {"k_actors": (round(ms3[0], 5) if cfgd["caps"]["actor_cap"] > 0 else None),
-                          "k_ego": round(ms3[1], 5), "k_raster": round(ms3[2], 5)},
-            "raster_ms_per_launch": None if burst_ms is None else round(burst_ms, 5),
-            "roofline": {"bound": "hbm", "kernel": "k_raster", "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "peak_measured": peak, **counter_fields,
-                         "traffic": traffic, "algorithmic_bytes_per_env": algo_bytes,
-                         "timing": (f"HIP events around {args.raster_reps} back-to-back launches on the step stream"
-                                    if burst_ms is not None else "HIP events around each launch in the timed steps"),
-                         # the same bytes over the per-step event time (includes each launch's dispatch gap)
-                         "achieved_step_events": round(n * algo_bytes / (ms3[2] * 1e-3) / 1e9, 1)},
-            "with_wire_obs": None if wire_value is None else round(wire_value, 1),
-            "fresh_resets": fresh,
-            # the reference surface's own loop (INTEGRATION.md §1), host scene builds included
-            "surface_loop": surf,
-            "surface_loop_fresh": surf_fresh,
             "gather_bytes_per_step": None if gatherer is None else gatherer.bytes_per_step,
-            "cpu_baseline": cpu,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
+        if args.full:
+            out.update(full_fields, cpu_baseline=cpu)
         print(json.dumps(out), flush=True)
     env.close()
+    warm_env.close()
     if pool is not None:
         pool.close()
     if bpool is not None:

@@ -6,6 +6,7 @@ set -u
 : "${CFG:?set CFG}"
 mkdir -p gpurun_out
 CACHE=/tmp/cbev_scene_cache
+BENCH_EXTRA="--full ${BENCH_EXTRA:-}"  # the whole line (roofline, CPU baseline, ...), not only the headline
 timeout -k 10 600 python -u bench.py --config $CFG --scene-cache $CACHE ${BENCH_EXTRA:-} > gpurun_out/bench_cfg$CFG.json 2> gpurun_out/bench_cfg$CFG.err || { echo "bench failed"; tail -5 gpurun_out/bench_cfg$CFG.err; exit 1; }
 tail -1 gpurun_out/bench_cfg$CFG.json
 OUT=gpurun_out/prof$CFG
