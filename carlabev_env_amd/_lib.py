@@ -70,6 +70,10 @@ def lib():
     L.cbev_flush.restype = _I
     L.cbev_expand_obs.argtypes = [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]
     L.cbev_expand_obs.restype = _I
+    L.cbev_expand_obs_typed.argtypes = [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P]
+    L.cbev_expand_obs_typed.restype = _I
+    L.cbev_unpack_obs.argtypes = [_P, _P, _I, _I, _I, _P, _P]
+    L.cbev_unpack_obs.restype = _I
     L.cbev_pack_frames.argtypes = [_P, _P, _I, _P, _P]
     L.cbev_pack_frames.restype = _I
     L.cbev_unpack_frames.argtypes = [_P, _P, _I, _P, _P]
@@ -115,7 +119,10 @@ EXPORTED_SYMBOLS = ("cbev_abi_version", "cbev_params_size", "cbev_layout_of", "c
                     "cbev_set_deferred_reset", "cbev_reset_pending", "cbev_flush",
                     "cbev_expand_obs", "cbev_vector_obs", "cbev_set_fov_mask", "cbev_set_obs_size", "cbev_resize_obs", "cbev_profile", "cbev_profile_read",
                     "cbev_profile_raster", "cbev_error_flags", "cbev_set_episode_stats", "cbev_episode_slot",
-                    "cbev_wall_clock_hz", "cbev_termination_count", "cbev_pack_frames", "cbev_unpack_frames")
+                    "cbev_wall_clock_hz", "cbev_termination_count", "cbev_pack_frames", "cbev_unpack_frames",
+                    "cbev_expand_obs_typed", "cbev_unpack_obs")
+
+OBS_F32, OBS_F16, OBS_U8, OBS_BITS = 0, 1, 2, 3  # CBEV_OBS_* (include/cbev.h)
 
 ERR_ACTION_INDEX = 1  # CBEV_ERR_ACTION_INDEX (include/cbev.h)
 ERR_RASTER_WINDOW = 2  # CBEV_ERR_RASTER_WINDOW (include/cbev.h)

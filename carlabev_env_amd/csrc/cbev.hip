@@ -3348,6 +3348,7 @@ struct Lut16 {
 // read by the learner later, so it should not evict the map and records from L2.
 typedef float nt_f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t nt_u4 __attribute__((ext_vector_type(4)));
+typedef uint32_t nt_u2 __attribute__((ext_vector_type(2)));
 
 template <int V>
 __device__ __forceinline__ void store_nt(float* d, const float* v) {
@@ -3430,6 +3431,302 @@ __global__ __launch_bounds__(256) void k_expand_semantic(const uint8_t* __restri
   }
 }
 
+// ---- compact wire types of the semantic expansion (cbev_expand_obs_typed) ----
+// The same ring, Lut16 channel masks, FUSE kinds and channel order as
+// k_expand_semantic; every value of a semantic observation is 0 or 1 (FUSE 2's
+// last channel: a multiple of 0.25), so the narrower types are lossless:
+//   T = _Float16  __half[n][Cout][h][w], 8 pixels per thread and 16-byte store
+//   T = uint8_t   uint8[n][Cout][h][w] (FUSE 0 / 1), 16 pixels per 16-byte store
+// V = 1 is the byte-granular path (h*w not a multiple of 16 / sizeof(T), or
+// pointers that are not 16-byte aligned). Stores are streamed as above.
+typedef _Float16 nt_h8 __attribute__((ext_vector_type(8)));
+
+template <int V>
+__device__ __forceinline__ void load_masks_w(const uint8_t* src, const Lut16& lut, uint32_t* m) {
+  if constexpr (V == 1) {
+    m[0] = lut.v[src[0] & 15];
+  } else {
+    uint32_t w[V / 4];
+    if constexpr (V == 16) {
+      const uint4 x = *(const uint4*)src;
+      w[0] = x.x, w[1] = x.y, w[2] = x.z, w[3] = x.w;
+    } else {
+      const uint2 x = *(const uint2*)src;
+      w[0] = x.x, w[1] = x.y;
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) m[k] = lut.v[(w[k >> 2] >> (8 * (k & 3))) & 15];
+  }
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void store_ntw(T* d, const T* v) {
+  if constexpr (V == 1) {
+    __builtin_nontemporal_store(v[0], d);
+  } else if constexpr (sizeof(T) == 2) {
+    nt_h8 x;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = v[k];
+    __builtin_nontemporal_store(x, (nt_h8*)d);
+  } else {
+    nt_u4 x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      x[j] = (uint32_t)v[4 * j] | ((uint32_t)v[4 * j + 1] << 8) | ((uint32_t)v[4 * j + 2] << 16) |
+             ((uint32_t)v[4 * j + 3] << 24);
+    __builtin_nontemporal_store(x, (nt_u4*)d);
+  }
+}
+
+template <int FUSE, typename T, int V>
+__global__ __launch_bounds__(256) void k_expand_semantic_w(const uint8_t* __restrict__ ring, int n, int F, int head, int C,
+                                                           int vidx, int SS, Lut16 lut, T* __restrict__ out) {
+  const int nv = SS / V;
+  const int Cout = FUSE == 0 ? F * C : (FUSE == 1 ? C + 2 : C);
+  const int64_t total = (int64_t)n * nv;
+  for (int64_t q = blockIdx.x * 256ll + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+    const int64_t e = q / nv;
+    const int64_t p = (q - e * nv) * V;
+    T* o = out + e * Cout * (int64_t)SS + p;
+    T vals[V];
+    if (FUSE == 0) {
+      for (int f = 0; f < F; ++f) {  // oldest -> newest
+        const int slot = (head + 1 + f) % F;
+        uint32_t m[V];
+        load_masks_w<V>(ring + ((int64_t)slot * n + e) * SS + p, lut, m);
+        for (int c = 0; c < C; ++c) {
+#pragma unroll
+          for (int k = 0; k < V; ++k) vals[k] = (T)((m[k] >> c) & 1);
+          store_ntw<T, V>(o + (int64_t)(f * C + c) * SS, vals);
+        }
+      }
+    } else {
+      uint32_t m0[V], m1[V], m2[V];  // newest, newest-1, newest-2
+      load_masks_w<V>(ring + ((int64_t)head * n + e) * SS + p, lut, m0);
+      load_masks_w<V>(ring + ((int64_t)((head - 1 + F) % F) * n + e) * SS + p, lut, m1);
+      load_masks_w<V>(ring + ((int64_t)((head - 2 + 2 * F) % F) * n + e) * SS + p, lut, m2);
+      int oc = 0;
+      for (int c = 0; c < C; ++c) {  // static channels of the newest frame
+        if (c == vidx) continue;
+#pragma unroll
+        for (int k = 0; k < V; ++k) vals[k] = (T)((m0[k] >> c) & 1);
+        store_ntw<T, V>(o + (int64_t)(oc++) * SS, vals);
+      }
+      if (FUSE == 1) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) vals[k] = (T)((m0[k] >> vidx) & 1);
+        store_ntw<T, V>(o + (int64_t)oc * SS, vals);
+#pragma unroll
+        for (int k = 0; k < V; ++k) vals[k] = (T)((m1[k] >> vidx) & 1);
+        store_ntw<T, V>(o + (int64_t)(oc + 1) * SS, vals);
+#pragma unroll
+        for (int k = 0; k < V; ++k) vals[k] = (T)((m2[k] >> vidx) & 1);
+        store_ntw<T, V>(o + (int64_t)(oc + 2) * SS, vals);
+      } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) {  // float32 in the reference's order, clipped, then converted
+          float acc = 0.0f;
+          acc += 1.0f * (float)((m0[k] >> vidx) & 1);
+          acc += 0.5f * (float)((m1[k] >> vidx) & 1);
+          acc += 0.25f * (float)((m2[k] >> vidx) & 1);
+          vals[k] = (T)fminf(fmaxf(acc, 0.0f), 1.0f);
+        }
+        store_ntw<T, V>(o + (int64_t)oc * SS, vals);
+      }
+    }
+  }
+}
+
+// Bit-packed planes (FUSE 0 / 1): uint8[n][Cout][PB], PB = ceil(h*w / 8); pixel
+// p of a plane is bit p & 7 of byte p >> 3 (numpy.packbits, bitorder="little"),
+// the unused high bits of a plane's last byte are zero.
+//   V = 32  h*w a multiple of 32: two 16-byte loads, one dword store per channel
+//   V = 8   any h*w: one output byte per thread and channel (an 8-byte load when
+//           h*w is a multiple of 8, else byte loads bounded by the plane's end);
+//           a plane then starts at any byte, so nothing wider can be stored
+// The Lut16 masks are transposed once per workgroup into LDS, idset[c] = the
+// 16-bit set of palette ids that set channel c, so a pixel's bit of channel c is
+// (idset[c] >> id) & 1: no per-pixel table load between the ring load and the
+// store, and the ids stay packed in registers ("Compact wire
+// observations": the kernel is VALU-bound, the versions measured).
+template <int V>
+__device__ __forceinline__ void load_ids_b(const uint8_t* src, int left, uint32_t* id) {
+  uint32_t w[V / 4];
+  if constexpr (V == 32) {
+    const uint4 a = *(const uint4*)src, b = *(const uint4*)(src + 16);
+    w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
+  } else if (left >= 8 && (((uintptr_t)src) & 7) == 0) {
+    const uint2 a = *(const uint2*)src;
+    w[0] = a.x, w[1] = a.y;
+  } else {
+    w[0] = w[1] = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (k < left) w[k >> 2] |= (uint32_t)src[k] << (8 * (k & 3));
+  }
+#pragma unroll
+  for (int k = 0; k < V; ++k) id[k] = (w[k >> 2] >> (8 * (k & 3))) & 15;
+}
+// `valid`: the bits of pixels inside the plane (pad bits are written as zero)
+template <int V>
+__device__ __forceinline__ uint32_t plane_bits(const uint32_t* id, uint32_t idset, uint32_t valid) {
+  uint32_t w = 0;
+#pragma unroll
+  for (int k = 0; k < V; ++k) w |= __builtin_amdgcn_ubfe(idset, id[k], 1u) << k;  // v_bfe_u32 + v_lshl_or_b32
+  return w & valid;
+}
+template <int V>
+__device__ __forceinline__ void store_bits(uint8_t* d, uint32_t w) {
+  if constexpr (V == 32)
+    __builtin_nontemporal_store(w, (uint32_t*)d);
+  else
+    __builtin_nontemporal_store((uint8_t)w, d);
+}
+
+template <int FUSE, int V>
+__global__ __launch_bounds__(256) void k_expand_semantic_bits(const uint8_t* __restrict__ ring, int n, int F, int head,
+                                                              int C, int vidx, int SS, Lut16 lut,
+                                                              uint8_t* __restrict__ out) {
+  __shared__ uint32_t idset[16];
+  if (threadIdx.x < 16) {
+    uint32_t t = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t |= ((lut.v[i] >> threadIdx.x) & 1u) << i;
+    idset[threadIdx.x] = t;
+  }
+  __syncthreads();
+  const int PB = (SS + 7) >> 3;
+  const int nv = (SS + V - 1) / V;
+  const int Cout = FUSE == 0 ? F * C : C + 2;
+  const int64_t total = (int64_t)n * nv;
+  for (int64_t q = blockIdx.x * 256ll + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+    const int64_t e = q / nv;
+    const int j = (int)(q - e * nv);
+    const int p = j * V, left = SS - p;
+    const uint32_t valid = left >= V ? 0xffffffffu : (1u << left) - 1u;
+    uint8_t* o = out + e * Cout * (int64_t)PB + j * (V / 8);
+    uint32_t id[V];
+    if (FUSE == 0) {
+      for (int f = 0; f < F; ++f) {  // oldest -> newest
+        const int slot = (head + 1 + f) % F;
+        load_ids_b<V>(ring + ((int64_t)slot * n + e) * SS + p, left, id);
+        for (int c = 0; c < C; ++c) store_bits<V>(o + (int64_t)(f * C + c) * PB, plane_bits<V>(id, idset[c], valid));
+      }
+    } else {
+      const uint32_t vset = idset[vidx];
+      load_ids_b<V>(ring + ((int64_t)((head - 1 + F) % F) * n + e) * SS + p, left, id);
+      const uint32_t v1 = plane_bits<V>(id, vset, valid);
+      load_ids_b<V>(ring + ((int64_t)((head - 2 + 2 * F) % F) * n + e) * SS + p, left, id);
+      const uint32_t v2 = plane_bits<V>(id, vset, valid);
+      load_ids_b<V>(ring + ((int64_t)head * n + e) * SS + p, left, id);
+      int oc = 0;
+      for (int c = 0; c < C; ++c) {  // static channels of the newest frame
+        if (c == vidx) continue;
+        store_bits<V>(o + (int64_t)(oc++) * PB, plane_bits<V>(id, idset[c], valid));
+      }
+      store_bits<V>(o + (int64_t)oc * PB, plane_bits<V>(id, vset, valid));
+      store_bits<V>(o + (int64_t)(oc + 1) * PB, v1);
+      store_bits<V>(o + (int64_t)(oc + 2) * PB, v2);
+    }
+  }
+}
+
+#ifdef CBEV_BITS_BALLOT
+// The measured alternative of the V = 32 path ("Compact wire
+// observations"): a wave takes 256 pixels, lane l loads pixels 64r + l, one
+// __ballot per (r, channel) yields 64 pixels of a plane, and lanes 0..7 store
+// the four ballot words as 8 dwords. h*w a multiple of 256.
+template <int FUSE>
+__global__ __launch_bounds__(256) void k_expand_semantic_ballot(const uint8_t* __restrict__ ring, int n, int F, int head,
+                                                                int C, int vidx, int SS, Lut16 lut,
+                                                                uint8_t* __restrict__ out) {
+  const int PB = SS >> 3, nv = SS >> 8;
+  const int lane = threadIdx.x & 63;
+  const int Cout = FUSE == 0 ? F * C : C + 2;
+  const int64_t total = (int64_t)n * nv;
+  auto emit = [&](uint8_t* d, const uint32_t* m, int c) {
+    uint64_t b[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) b[r] = __ballot((m[r] >> c) & 1u);
+    const int r = lane >> 1;
+    const uint64_t x = r == 0 ? b[0] : (r == 1 ? b[1] : (r == 2 ? b[2] : b[3]));
+    const uint32_t w = (lane & 1) ? (uint32_t)(x >> 32) : (uint32_t)x;
+    if (lane < 8) __builtin_nontemporal_store(w, (uint32_t*)d + lane);
+  };
+  auto load = [&](int slot, int64_t e, int p, uint32_t* m) {
+    const uint8_t* src = ring + ((int64_t)slot * n + e) * SS + p + lane;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) m[r] = lut.v[src[64 * r] & 15];
+  };
+  for (int64_t q = blockIdx.x * 4ll + (threadIdx.x >> 6); q < total; q += (int64_t)gridDim.x * 4) {
+    const int64_t e = q / nv;
+    const int j = (int)(q - e * nv);
+    uint8_t* o = out + e * Cout * (int64_t)PB + j * 32;
+    uint32_t m[4];
+    if (FUSE == 0) {
+      for (int f = 0; f < F; ++f) {
+        load((head + 1 + f) % F, e, j * 256, m);
+        for (int c = 0; c < C; ++c) emit(o + (int64_t)(f * C + c) * PB, m, c);
+      }
+    } else {
+      uint32_t m1[4], m2[4];
+      load(head, e, j * 256, m);
+      load((head - 1 + F) % F, e, j * 256, m1);
+      load((head - 2 + 2 * F) % F, e, j * 256, m2);
+      int oc = 0;
+      for (int c = 0; c < C; ++c) {
+        if (c == vidx) continue;
+        emit(o + (int64_t)(oc++) * PB, m, c);
+      }
+      emit(o + (int64_t)oc * PB, m, vidx);
+      emit(o + (int64_t)(oc + 1) * PB, m1, vidx);
+      emit(o + (int64_t)(oc + 2) * PB, m2, vidx);
+    }
+  }
+}
+#endif
+
+// The learner's side of the bit-packed planes: packed uint8[rows][ceil(P / 8)]
+// -> T[rows][P] (float32, float16 or uint8 0 / 1). WIDE (P a multiple of 8,
+// 16-byte-aligned out): one packed byte per thread, its 8 pixels stored as 32,
+// 16 or 8 bytes; otherwise one pixel per thread.
+template <typename T, bool WIDE>
+__global__ __launch_bounds__(256) void k_unpack_bits(const uint8_t* __restrict__ packed, int64_t rows, int P,
+                                                     T* __restrict__ out) {
+  if constexpr (WIDE) {
+    const int64_t total = rows * (int64_t)(P >> 3);  // rows are contiguous on both sides
+    for (int64_t q = blockIdx.x * 256ll + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+      const uint32_t b = packed[q];
+      T* d = out + 8 * q;
+      if constexpr (sizeof(T) == 4) {
+        const nt_f4 lo = {(float)(b & 1), (float)((b >> 1) & 1), (float)((b >> 2) & 1), (float)((b >> 3) & 1)};
+        const nt_f4 hi = {(float)((b >> 4) & 1), (float)((b >> 5) & 1), (float)((b >> 6) & 1), (float)((b >> 7) & 1)};
+        __builtin_nontemporal_store(lo, (nt_f4*)d);
+        __builtin_nontemporal_store(hi, (nt_f4*)d + 1);
+      } else if constexpr (sizeof(T) == 2) {
+        nt_h8 x;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = (_Float16)((b >> k) & 1);
+        __builtin_nontemporal_store(x, (nt_h8*)d);
+      } else {
+        // bit k -> byte k: spread the low and the high nibble over a dword each
+        const uint32_t lo = b & 15u, hi = b >> 4;
+        const nt_u2 x = {(lo | (lo << 7) | (lo << 14) | (lo << 21)) & 0x01010101u,
+                         (hi | (hi << 7) | (hi << 14) | (hi << 21)) & 0x01010101u};
+        __builtin_nontemporal_store(x, (nt_u2*)d);
+      }
+    }
+  } else {
+    const int PB = (P + 7) >> 3;
+    const int64_t total = rows * (int64_t)P;
+    for (int64_t q = blockIdx.x * 256ll + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+      const int64_t r = q / P;
+      const int p = (int)(q - r * P);
+      out[q] = (T)((packed[r * PB + (p >> 3)] >> (p & 7)) & 1);
+    }
+  }
+}
+
 // Grayscale + frame stack: out[e][f][p] (uint8), oldest first. RAW: the ring
 // already holds gray values (the resize path), copied as they are.
 template <bool RAW, int V>
@@ -3484,7 +3781,6 @@ __global__ __launch_bounds__(256) void k_expand_rgb(const uint8_t* __restrict__ 
 // The wire format of the multi-GPU frame gather (sharding.FrameGather): half
 // the bytes of the uint8 frames. 16 pixels per thread, one 16-byte load and one
 // 8-byte store (pack) or the reverse (unpack), streamed (non-temporal).
-typedef uint32_t nt_u2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack8(uint32_t a, uint32_t b) {  // 8 ids (two dwords) -> 8 nibbles
   const uint32_t x = (a & 0x0f0f0f0fu) | ((a >> 4) & 0xf0f0f0f0u);    // bytes 0|1<<4 in byte 0, 2|3<<4 in byte 2
   const uint32_t y = (b & 0x0f0f0f0fu) | ((b >> 4) & 0xf0f0f0f0u);
@@ -4437,6 +4733,126 @@ int cbev_expand_obs(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int h
     default:
       return set_err(CBEV_EINVAL, "unknown expansion kind %d", kind);
   }
+  HIP_TRY(hipGetLastError());
+  return CBEV_OK;
+}
+
+int cbev_expand_obs_typed(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int head, int kind, int n_channels,
+                          const uint32_t* lut_host, int out_dtype, void* out, void* stream) {
+  if (!c || !ring || !out) return set_err(CBEV_EINVAL, "null argument");
+  // the refusals of the wire type come first: nothing is launched, the deferred reset included
+  if (out_dtype < CBEV_OBS_F32 || out_dtype > CBEV_OBS_BITS) return set_err(CBEV_EINVAL, "unknown obs dtype %d", out_dtype);
+  if (kind == 1 || kind == 2 || kind == 5) {
+    if (out_dtype != CBEV_OBS_U8)
+      return set_err(CBEV_EINVAL, "expansion kind %d is uint8: obs dtype %d does not apply", kind, out_dtype);
+    return cbev_expand_obs(c, ring, n, n_frames, head, kind, n_channels, lut_host, out, stream);
+  }
+  if (kind == 4 && (out_dtype == CBEV_OBS_U8 || out_dtype == CBEV_OBS_BITS))
+    return set_err(CBEV_EINVAL, "the weighted vehicle history is fractional: obs dtype %d cannot hold it", out_dtype);
+  if (out_dtype == CBEV_OBS_F32 || !(kind == 0 || kind == 3 || kind == 4))
+    return cbev_expand_obs(c, ring, n, n_frames, head, kind, n_channels, lut_host, out, stream);
+  CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
+  if (!lut_host) return set_err(CBEV_EINVAL, "null lut");
+  if (n_frames < 1 || head < 0 || head >= n_frames) return set_err(CBEV_EINVAL, "bad frame ring");
+  if (n_channels < 1 || n_channels > 16) return set_err(CBEV_EINVAL, "bad channel count");
+  Lut16 lut{};
+  memcpy(lut.v, lut_host, sizeof lut.v);
+  int vidx = -1;
+  if (kind != 0) {  // as cbev_expand_obs
+    const uint32_t vm = lut.v[CBEV_PX_VEHICLE];
+    if (vm == 0 || (vm & (vm - 1)) != 0 || vm >= (1u << n_channels))
+      return set_err(CBEV_EINVAL, "vehicle history fusion needs a semantic mode with a vehicle channel");
+    vidx = __builtin_ctz(vm);
+    if (n_frames < 3) return set_err(CBEV_EINVAL, "vehicle history fusion requires frame_stack >= 3");
+  }
+  if (n <= 0) return CBEV_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int SS = c->obs_h * c->obs_w;
+  const bool al16 = ((((uintptr_t)ring) | ((uintptr_t)out)) & 15) == 0;
+  // V pixels per thread: the widest the pixel count and the pointers allow
+  const int V = out_dtype == CBEV_OBS_F16 ? (al16 && SS % 8 == 0 ? 8 : 1)
+                : out_dtype == CBEV_OBS_U8 ? (al16 && SS % 16 == 0 ? 16 : 1)
+                                           : (al16 && SS % 32 == 0 ? 32 : 8);
+  const int64_t threads = (int64_t)n * ((SS + V - 1) / V);
+  const int grid = (int)std::min<int64_t>((threads + 255) / 256, 4096);
+#define TYPED_LAUNCH(KERNEL, OUT_T)                                                                               \
+  hipLaunchKernelGGL((KERNEL), dim3(grid), dim3(256), 0, s, ring, n, n_frames, head, n_channels, vidx, SS, lut, \
+                     (OUT_T*)out)
+#ifdef CBEV_BITS_BALLOT
+#define BITS_WIDE_LAUNCH(FUSE)                                 \
+  do {                                                         \
+    if (SS % 256 == 0) {                                       \
+      TYPED_LAUNCH((k_expand_semantic_ballot<FUSE>), uint8_t); \
+    } else {                                                   \
+      TYPED_LAUNCH((k_expand_semantic_bits<FUSE, 32>), uint8_t); \
+    }                                                          \
+  } while (0)
+#else
+#define BITS_WIDE_LAUNCH(FUSE) TYPED_LAUNCH((k_expand_semantic_bits<FUSE, 32>), uint8_t)
+#endif
+#define TYPED_FUSE(FUSE)                                                \
+  switch (out_dtype) {                                                  \
+    case CBEV_OBS_F16:                                                  \
+      if (V == 8) {                                                     \
+        TYPED_LAUNCH((k_expand_semantic_w<FUSE, _Float16, 8>), _Float16); \
+      } else {                                                          \
+        TYPED_LAUNCH((k_expand_semantic_w<FUSE, _Float16, 1>), _Float16); \
+      }                                                                 \
+      break;                                                            \
+    case CBEV_OBS_U8:                                                   \
+      if (V == 16) {                                                    \
+        TYPED_LAUNCH((k_expand_semantic_w<FUSE, uint8_t, 16>), uint8_t); \
+      } else {                                                          \
+        TYPED_LAUNCH((k_expand_semantic_w<FUSE, uint8_t, 1>), uint8_t); \
+      }                                                                 \
+      break;                                                            \
+    default:                                                            \
+      if (V == 32) {                                                    \
+        BITS_WIDE_LAUNCH(FUSE);                                         \
+      } else {                                                          \
+        TYPED_LAUNCH((k_expand_semantic_bits<FUSE, 8>), uint8_t);       \
+      }                                                                 \
+      break;                                                            \
+  }
+  if (kind == 0) {
+    TYPED_FUSE(0)
+  } else if (kind == 3) {
+    TYPED_FUSE(1)
+  } else if (V == 8) {  // kind 4: float16 only (refused above otherwise)
+    TYPED_LAUNCH((k_expand_semantic_w<2, _Float16, 8>), _Float16);
+  } else {
+    TYPED_LAUNCH((k_expand_semantic_w<2, _Float16, 1>), _Float16);
+  }
+#undef BITS_WIDE_LAUNCH
+#undef TYPED_FUSE
+#undef TYPED_LAUNCH
+  HIP_TRY(hipGetLastError());
+  return CBEV_OK;
+}
+
+int cbev_unpack_obs(cbev_ctx* c, const uint8_t* packed, int rows, int pixels, int out_dtype, void* out, void* stream) {
+  if (!c || !packed || !out) return set_err(CBEV_EINVAL, "null argument");
+  if (out_dtype != CBEV_OBS_F32 && out_dtype != CBEV_OBS_F16 && out_dtype != CBEV_OBS_U8)
+    return set_err(CBEV_EINVAL, "unpack to obs dtype %d", out_dtype);
+  if (rows < 0 || pixels < 1) return set_err(CBEV_EINVAL, "unpack of %d rows of %d pixels", rows, pixels);
+  if (rows == 0) return CBEV_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = pixels % 8 == 0 && (((uintptr_t)out) & 15) == 0;
+  const int64_t threads = (int64_t)rows * (wide ? pixels / 8 : pixels);
+  const int grid = (int)std::min<int64_t>((threads + 255) / 256, 16384);
+#define UNPACK_LAUNCH(T)                                                                                          \
+  if (wide)                                                                                                       \
+    hipLaunchKernelGGL((k_unpack_bits<T, true>), dim3(grid), dim3(256), 0, s, packed, (int64_t)rows, pixels, (T*)out); \
+  else                                                                                                            \
+    hipLaunchKernelGGL((k_unpack_bits<T, false>), dim3(grid), dim3(256), 0, s, packed, (int64_t)rows, pixels, (T*)out)
+  if (out_dtype == CBEV_OBS_F32) {
+    UNPACK_LAUNCH(float);
+  } else if (out_dtype == CBEV_OBS_F16) {
+    UNPACK_LAUNCH(_Float16);
+  } else {
+    UNPACK_LAUNCH(uint8_t);
+  }
+#undef UNPACK_LAUNCH
   HIP_TRY(hipGetLastError());
   return CBEV_OK;
 }

@@ -44,6 +44,61 @@ def fused_channels(mode: str, fusion: str, frame_stack: int = 4) -> int:
     raise ValueError(f"unknown temporal_fusion_mode {fusion!r}")
 
 
+# Wire types of the semantic observation (cbev_expand_obs_typed, CBEV_OBS_*): the
+# index is the C-ABI code. Every value is 0 or 1, vehicle_weighted's last channel
+# a multiple of 0.25, so float16 is lossless for all fusions and uint8 / bits for
+# the two whose values are all 0 or 1.
+OBS_DTYPES = ("float32", "float16", "uint8", "bits")
+
+
+def obs_dtype_code(obs_dtype: str) -> int:
+    if obs_dtype not in OBS_DTYPES:
+        raise ValueError(f"unknown obs_dtype {obs_dtype!r}: one of {OBS_DTYPES}")
+    return OBS_DTYPES.index(obs_dtype)
+
+
+def wire_obs_spec(mode: str, fusion: str, frame_stack: int, hw, obs_dtype: str = "float32"):
+    """(shape, numpy dtype, low, high) of one env's wrapped semantic observation
+    in the wire type `obs_dtype`:
+
+      float32 | float16 | uint8   (Cw, h, w), values in [0, 1]
+      bits                        (Cw, ceil(h*w / 8)) uint8 in [0, 255]: pixel p of a
+                                  channel plane is bit p & 7 of byte p >> 3
+
+    Cw = fused_channels(mode, fusion, frame_stack). uint8 and bits cannot hold
+    vehicle_weighted's fractional channel: ValueError."""
+    obs_dtype_code(obs_dtype)
+    if obs_dtype in ("uint8", "bits") and fusion == "vehicle_weighted":
+        raise ValueError(f"obs_dtype={obs_dtype!r} cannot hold temporal_fusion_mode='vehicle_weighted' "
+                         "(its vehicle channel is fractional); use 'float16' or 'float32'")
+    Cw = fused_channels(mode, fusion, frame_stack)
+    h, w = int(hw[0]), int(hw[1])
+    if obs_dtype == "bits":
+        return (Cw, (h * w + 7) // 8), np.dtype(np.uint8), 0, 255
+    return (Cw, h, w), np.dtype({"float32": np.float32, "float16": np.float16, "uint8": np.uint8}[obs_dtype]), 0, 1
+
+
+def pack_bits_ref(x) -> np.ndarray:
+    """The `bits` layout in numpy: x[..., P] of 0 / 1 -> uint8[..., ceil(P / 8)],
+    pixel p in bit p & 7 of byte p >> 3, the last byte's unused high bits 0."""
+    x = np.asarray(x)
+    P = x.shape[-1]
+    nb = (P + 7) // 8
+    bits = np.zeros(x.shape[:-1] + (nb * 8,), np.uint8)
+    bits[..., :P] = x != 0
+    weights = (1 << np.arange(8)).astype(np.uint16)
+    return (bits.reshape(x.shape[:-1] + (nb, 8)) * weights).sum(-1).astype(np.uint8)
+
+
+def unpack_bits_ref(packed, pixels: int, dtype=np.float32) -> np.ndarray:
+    """Inverse of pack_bits_ref: uint8[..., ceil(pixels / 8)] -> dtype[..., pixels]."""
+    packed = np.asarray(packed, np.uint8)
+    if packed.shape[-1] != (pixels + 7) // 8:
+        raise ValueError(f"{packed.shape[-1]} packed bytes do not hold {pixels} pixels")
+    bits = (packed[..., :, None] >> np.arange(8, dtype=np.uint8)) & 1
+    return bits.reshape(packed.shape[:-1] + (-1,))[..., :pixels].astype(dtype)
+
+
 def area_table(ssize: int, dsize: int):
     """computeResizeAreaTab (opencv 4.11 resize.cpp) for scale = 1 / (dsize / ssize),
     grouped per destination index: (off[dsize + 1], src index, float32 alpha)."""

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import layout as LY
-from ._lib import check, lib
+from ._lib import OBS_F16, OBS_F32, OBS_U8, check, lib
 from .config import EnvConfig, RunConfig, validate_run_config, get_action_profile_spec
 from .params import CbevParams, build_params, load_class_map, padded_map
 from .host_reset import HostResetBuilder
@@ -120,7 +120,7 @@ class CarlaBEVVectorEnv:
 
     def __init__(self, cfg, *, num_envs: int | None = None, device=None, caps: dict | None = None,
                  info_mode: str = "full", scene_generator=None, wrappers: bool = True, copy_obs: bool = True,
-                 defer_reset: bool = True, reset_pool=None):
+                 defer_reset: bool = True, reset_pool=None, obs_dtype: str = "float32"):
         """wrappers=False gives the base `CarlaBEV` observation of every env, as a
         `SyncVectorEnv` of unwrapped `CarlaBEV(cfg)` would: (S, S, 3) uint8 RGB for the
         BEV modes, float32[7] for obs_mode="vector" (carlabev.py:233-244, spaces.py:54-61).
@@ -153,7 +153,16 @@ class CarlaBEVVectorEnv:
         GPU) that builds the distinct scenes a reset(options) needs in worker
         processes; records are byte-identical to the in-process build. Built scenes
         are memoised either way (HostResetBuilder), so a repeated (seed, options)
-        reset, such as the reference's canonical loop without seeds, is a copy."""
+        reset, such as the reference's canonical loop without seeds, is a copy.
+
+        obs_dtype: the wire type of the wrapped obs_mode="bev_semantic" observation
+        (obs_pipeline.OBS_DTYPES). "float32" (default) is the reference's; every
+        value is 0 or 1 (vehicle_weighted's last channel a multiple of 0.25), so
+        "float16", "uint8" and "bits" (one bit per pixel: uint8[Cw][ceil(h*w/8)],
+        pixel p in bit p & 7 of byte p >> 3; unpack_obs() expands it) carry the same
+        observation in 1/2, 1/4 and 1/32 of the bytes. "uint8" and "bits" refuse
+        vehicle_weighted; every other observation mode (gray, wrappers=False)
+        is uint8 or 7 floats already and refuses anything but "float32"."""
         if isinstance(cfg, RunConfig):
             raw = cfg
         elif isinstance(cfg, dict) and "env" in cfg:
@@ -166,6 +175,11 @@ class CarlaBEVVectorEnv:
         self.copy_obs = bool(copy_obs)
         self.run_cfg = run
         self.cfg: EnvConfig = run.env
+        self.obs_dtype = str(obs_dtype)
+        self._obs_code = OP.obs_dtype_code(self.obs_dtype)
+        if self.obs_dtype != "float32" and not (self.wrappers and self.cfg.masked):
+            raise ValueError(f"obs_dtype={self.obs_dtype!r} applies to the wrapped obs_mode='bev_semantic' observation "
+                             "only; this env's observation (gray stack, RGB or vector) takes obs_dtype='float32'")
         self.num_envs = int(num_envs if num_envs is not None else run.num_envs)
         self.info_mode = info_mode
         if device is None:
@@ -248,13 +262,19 @@ class CarlaBEVVectorEnv:
             C = len(self.channels)
             fusion = self.cfg.temporal_fusion_mode
             Cw = OP.fused_channels(self.cfg.semantic_mask_ch, fusion, F)
-            self.single_observation_space = make_box(0.0, 1.0, (Cw, h, w), np.float32)
             self._obs_kind, self._obs_lut, self._obs_ch = OP.FUSION_KIND[fusion], semantic_lut(self.cfg.semantic_mask_ch), C
-            self.obs_buf = torch.zeros((N, Cw, h, w), dtype=torch.float32, device=dev)
+            if self.obs_dtype == "float32":
+                self.single_observation_space = make_box(0.0, 1.0, (Cw, h, w), np.float32)
+                self.obs_buf = torch.zeros((N, Cw, h, w), dtype=torch.float32, device=dev)
+            else:
+                shape, dt, low, high = OP.wire_obs_spec(self.cfg.semantic_mask_ch, fusion, F, (h, w), self.obs_dtype)
+                self.single_observation_space = make_box(low, high, shape, dt)
+                self.obs_buf = torch.zeros((N, *shape), dtype=getattr(torch, dt.name), device=dev)
         else:
             self.single_observation_space = make_box(0, 255, (F, h, w), np.uint8)
             self._obs_kind = OP.KIND_GRAY_RAW if self.resize else OP.KIND_GRAY
             self._obs_lut, self._obs_ch = gray_lut(), 1
+            self._obs_code = OBS_U8  # the gray kinds' own type
             self.obs_buf = torch.zeros((N, F, h, w), dtype=torch.uint8, device=dev)
         self.observation_space = batch_space(self.single_observation_space, N)
         self.action_space = batch_space(self.single_action_space, N)
@@ -746,9 +766,33 @@ class CarlaBEVVectorEnv:
                                             rgb_lut().ctypes.data_as(ctypes.c_void_p), _ptr(out),
                                             self._stream()), "cbev_expand_obs")
             return out
-        check(lib().cbev_expand_obs(self._ctx, _ptr(self.ring), self.num_envs, self.F, self.head, self._obs_kind,
-                                    self._obs_ch, self._obs_lut.ctypes.data_as(ctypes.c_void_p), _ptr(out),
-                                    self._stream()), "cbev_expand_obs")
+        check(lib().cbev_expand_obs_typed(self._ctx, _ptr(self.ring), self.num_envs, self.F, self.head, self._obs_kind,
+                                          self._obs_ch, self._obs_lut.ctypes.data_as(ctypes.c_void_p), self._obs_code,
+                                          _ptr(out), self._stream()), "cbev_expand_obs_typed")
+        return out
+
+    def unpack_obs(self, packed: torch.Tensor, dtype=torch.float32, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Expand obs_dtype="bits" observations on the device (cbev_unpack_obs):
+        packed uint8[..., Cw, ceil(h*w / 8)] (one step's observation, a rollout
+        buffer or a minibatch gathered from one) -> dtype[..., Cw, h, w], dtype one
+        of torch.float32 / float16 / uint8. `out`, if given, is filled and returned."""
+        h, w = self.obs_hw
+        nb = (h * w + 7) // 8
+        codes = {torch.float32: OBS_F32, torch.float16: OBS_F16, torch.uint8: OBS_U8}
+        if dtype not in codes:
+            raise ValueError(f"unpack_obs to {dtype}: one of torch.float32, torch.float16, torch.uint8")
+        if packed.dtype != torch.uint8 or packed.dim() < 2 or packed.shape[-1] != nb or packed.device != self.device:
+            raise ValueError(f"packed must be a uint8[..., Cw, {nb}] tensor on {self.device}, got "
+                             f"{packed.dtype}{tuple(packed.shape)} on {packed.device}")
+        packed = packed.contiguous()
+        shape = (*packed.shape[:-1], h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != dtype or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dtype}{shape} tensor on {self.device}")
+        rows = packed.numel() // nb
+        check(lib().cbev_unpack_obs(self._ctx, _ptr(packed), rows, h * w, codes[dtype], _ptr(out), self._stream()),
+              "cbev_unpack_obs")
         return out
 
     def step_infos(self):

@@ -201,6 +201,33 @@ int cbev_flush(cbev_ctx* ctx);
 int cbev_expand_obs(cbev_ctx* ctx, const uint8_t* ring, int n, int n_frames, int head, int kind, int n_channels,
                     const uint32_t* channel_lut_host, void* out, void* stream);
 
+/* Compact wire types of the semantic kinds (0, 3, 4). Every value of a semantic
+ * observation is 0 or 1 (kind 4's last channel: 0, 0.25, 0.5, 0.75 or 1), so
+ * these are lossless; Cout is the channel count of the kind above:
+ *   CBEV_OBS_F32   float32[n][Cout][h][w], cbev_expand_obs itself
+ *   CBEV_OBS_F16   float16[n][Cout][h][w] (kind 4: summed and clipped in float32, then converted)
+ *   CBEV_OBS_U8    uint8[n][Cout][h][w], 0 or 1; kinds 0 and 3
+ *   CBEV_OBS_BITS  uint8[n][Cout][ceil(h*w / 8)]: pixel p of a channel plane is
+ *                  bit p & 7 of byte p >> 3 (numpy.packbits(plane.reshape(-1),
+ *                  bitorder="little")), the unused high bits of a plane's last
+ *                  byte are 0; kinds 0 and 3
+ * cbev_expand_obs_typed takes cbev_expand_obs's arguments and checks, and returns
+ * CBEV_EINVAL before it launches anything for an unknown out_dtype, for kind 4
+ * with U8 or BITS, and for kinds 1, 2, 5 (uint8 already: they forward to
+ * cbev_expand_obs) with an out_dtype other than CBEV_OBS_U8. It allocates
+ * nothing (safe under stream capture). 16-byte-aligned ring and out take the
+ * wide kernels; any alignment of the element type is accepted.
+ * cbev_unpack_obs is the learner's side of CBEV_OBS_BITS: packed =
+ * uint8[rows][ceil(pixels / 8)] (any number of planes, e.g. a minibatch gathered
+ * from a rollout buffer) -> out[rows][pixels] of CBEV_OBS_F32, F16 or U8. */
+#define CBEV_OBS_F32 0
+#define CBEV_OBS_F16 1
+#define CBEV_OBS_U8 2
+#define CBEV_OBS_BITS 3
+int cbev_expand_obs_typed(cbev_ctx* ctx, const uint8_t* ring, int n, int n_frames, int head, int kind, int n_channels,
+                          const uint32_t* channel_lut_host, int out_dtype, void* out, void* stream);
+int cbev_unpack_obs(cbev_ctx* ctx, const uint8_t* packed, int rows, int pixels, int out_dtype, void* out, void* stream);
+
 /* obs_mode "vector" (CarlaBEV.render, carlabev.py:237-244): out = float32[n][7],
  * [x, y, yaw, v] of the hero state + its Stanley set point [cx, cy, cyaw] at
  * target_idx (stanley_controller.py:140-148), from the records as they are now. */
