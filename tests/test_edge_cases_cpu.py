@@ -1,0 +1,234 @@
+"""The authored edge cases (tests/edge_cases.py) on the CPU: their expected
+values are checked against statements independent of the C oracle, and their
+coverage is counted, so the GPU parity runs over them (test_gpu_edge_cases.py)
+can neither compare against a wrong oracle nor pass vacuously."""
+from __future__ import annotations
+
+import collections
+
+import numpy as np
+import pytest
+
+import oracle as O
+import edge_cases as EC
+import raster_ref
+from carlabev_env_amd import layout as LY
+from carlabev_env_amd import routes
+
+GEO_IDS = [f"{s}-{a}" for s, a in EC.GEOMETRIES]
+
+# Classes of raster_classes a geometry cannot reach, by name, with the reason.
+# A 0.01 degree heading scan at a mid-map, an offset and a clamped position
+# gives the same empty classes as the matrix.
+_ENCLOSED = ("the crop is ceil(2 hypot(mx, my)) texels wide, the circle through the output's farthest corner around "
+             "the anchor: at every heading the rotated surface covers the output and every sample lies inside the "
+             "crop (test_output_never_leaves_the_crop), so raster_fast holds for every step pose")
+_PARITY = ("crop_origin rounds half to even: with an odd crop every unclamped origin has one parity, and the clamped "
+           "origins (0 and render - crop) do not supply this value")
+_SMALL = "64 x 64 tiles: at most 92 window rows over at least 36 rows per pass, never more than 3 passes"
+_LARGE = "128 x 128 tiles: at least 128 window rows over at most 28 rows per pass, never fewer than 5 passes"
+_NC128 = "128 x 128 tiles: 9 to 13 chunks per window row, none of which divides 256"
+_NC64 = ("64 x 64 tiles: 5 to 7 chunks per row, and 4 only for a 64-texel row that starts on a 16-byte boundary, which "
+         "no heading of the scan does with this crop's anchor and origin parity")
+_ALWAYS = {"check": _ENCLOSED, "clipped": _ENCLOSED, "outside": _ENCLOSED}
+EXCLUDED = {
+    (64, 0.5): dict(_ALWAYS, ushift2=_PARITY, passes_gt4=_SMALL),
+    (64, 0.2): dict(_ALWAYS, ushift2=_PARITY, passes_gt4=_SMALL, nc_divides=_NC64),
+    (128, 0.5): dict(_ALWAYS, passes_le4=_LARGE, nc_divides=_NC128),
+    (128, 0.2): dict(_ALWAYS, ushift3=_PARITY, passes_le4=_LARGE, nc_divides=_NC128),
+    (256, 0.5): dict(_ALWAYS, ushift2=_PARITY, passes_le4=_LARGE, nc_divides=_NC128),
+    (256, 0.6): dict(_ALWAYS, ushift2=_PARITY, passes_le4=_LARGE, nc_divides=_NC128),
+}
+
+
+def _step_and_restate(P, padded, layout, orc, rec, action, frame):
+    """One oracle step into `frame`, and the NumPy restatement of the same frame
+    (drawn after the dynamics and before the collision pass consumes targets:
+    the post-step record with the pre-step visibility bits, kept as vis_draw)."""
+    before = rec.copy()
+    cause = orc.step_one(rec, np.ascontiguousarray(action), frame)
+    mid = rec.copy()
+    vmid, vbef = LY.RecordView(mid, layout), LY.RecordView(before, layout)
+    assert np.array_equal(vmid.vis_draw, vbef.vis)
+    vmid.vis[:] = vbef.vis
+    return cause, raster_ref.render(P, padded, vmid)
+
+
+def _painted_corner(P, padded, view):
+    """The crop's top-left texel after painting (pygame rotate's background): the
+    map texel, then the last rect over it in draw order (raster_ref.render's)."""
+    xm, ym = raster_ref.crop_origin(P, view.h("X"), view.h("Y"))
+    one = padded[ym:ym + 1, xm:xm + 1].copy()
+    for a in range(view.i("NACT")):
+        sz = int(view.ai[LY.AI["SIZE"], a])
+        raster_ref.paint(one, round(P.pad + view.ad[LY.AD["X"], a]) - sz // 2 - xm,
+                         round(P.pad + view.ad[LY.AD["Y"], a]) - sz // 2 - ym, sz, sz,
+                         3 if view.ai[LY.AI["KIND"], a] == 1 else 4)
+    nt = view.i("NROUTE")
+    for i in range(nt):
+        if (int(view.vis_draw[i >> 5]) >> (i & 31)) & 1:
+            sz = 2 if i < nt - 1 else 4
+            raster_ref.paint(one, round(P.pad + view.cx[i]) - sz // 2 - xm, round(P.pad + view.cy[i]) - sz // 2 - ym,
+                             sz, sz, 5)
+    for k in range(view.i("NTL")):
+        t = view.ti[:, k]
+        raster_ref.paint(one, int(t[LY.TI["RX"]]) - xm, int(t[LY.TI["RY"]]) - ym, int(t[LY.TI["RW"]]),
+                         int(t[LY.TI["RH"]]), int(t[LY.TI["COLOR"]]))
+    return int(one[0, 0])
+
+
+@pytest.mark.parametrize("geo", EC.GEOMETRIES, ids=GEO_IDS)
+def test_raster_matrix_oracle_equals_numpy_and_covers_every_class(geo):
+    size, ay = geo
+    P, padded, caps, recs, layout, acts = EC.raster_batch(size, ay)
+    orc = O.Oracle(P, padded, caps.c(), layout.record_bytes)
+    S = P.size
+    frame = np.zeros((S, S), np.uint8)
+    hist, colours, bg_differs = collections.Counter(), collections.Counter(), 0
+    for e in range(len(recs)):
+        v = LY.RecordView(recs[e], layout)
+        orc.reset_obs(recs[e], frame)
+        ref = raster_ref.render(P, padded, v, reset=True)
+        assert np.array_equal(frame, ref), ("reset", e, np.argwhere(frame != ref)[:5])
+        pose = (v.h("X"), v.h("Y"), v.h("YAW"))
+        _, ref = _step_and_restate(P, padded, layout, orc, recs[e], acts[0, e], frame)
+        assert np.array_equal(frame, ref), ("step", e, np.argwhere(frame != ref)[:5])
+        # V = 0 and nothing pressed: the pose the case was authored at is the pose rendered
+        # (the step wraps the yaw into [-pi, pi), so angles below -90 render as angle + 360)
+        assert (v.h("X"), v.h("Y")) == pose[:2] and _angles_close(v.h("YAW"), pose[2], 1e-12)
+        labels = set()
+        for t in EC.raster_classes(P, v.h("X"), v.h("Y"), v.h("YAW")):
+            labels.update(EC.class_labels(t))
+            assert t["lds"] <= {64: 10672, 128: 38584, 256: 38584}[size]  # Tiles::lds_bytes
+        hist.update(labels)
+        if "check" in labels and _painted_corner(P, padded, v) != padded[raster_ref.crop_origin(P, *pose[:2])[::-1]]:
+            bg_differs += 1
+        inner = frame.copy()
+        hx, hy = P.anchor_x - P.hero_w // 2, P.anchor_y - P.hero_w // 2
+        inner[hy:hy + P.hero_w, hx:hx + P.hero_w] = 0  # the hero overlay is the only black
+        colours.update(np.unique(inner).tolist())
+    print(f"\n{size} x {size}, anchor_y {ay}, crop {P.crop}, {len(recs)} envs:",
+          {k: hist.get(k, 0) for k in EC.ALL_CLASSES})
+    excluded = EXCLUDED[geo]
+    for k in EC.ALL_CLASSES:
+        if k in excluded:
+            assert hist.get(k, 0) == 0, (k, "is reached after all: take it off the exclusions table")
+        else:
+            assert hist.get(k, 0) >= 3, (geo, k, hist.get(k, 0))
+    # a geometry that reaches the checked output must see painted crop backgrounds there
+    assert "check" in excluded or bg_differs >= 3, (geo, bg_differs)
+    # the painted content is seen: vehicle, pedestrian, route / green, red, yellow
+    for c in (3, 4, 5, 6, 7):
+        assert colours[c] >= 3, (geo, c, colours)
+    assert colours[8] == 0  # no black outside the rotated surface: it always covers the output (_ENCLOSED)
+
+
+@pytest.mark.parametrize("geo", EC.GEOMETRIES, ids=GEO_IDS)
+def test_output_never_leaves_the_crop(geo):
+    """The reason 'check', 'clipped' and 'outside' are on the exclusions table,
+    from the NumPy restatement alone: over a sentinel crop whose texel (0, 0) (the
+    rotozoom background) differs from the rest, no heading's frame holds the
+    background or the black outside the rotated surface. So a step pose cannot
+    reach tile_out_check or crop_background at these geometries, and the
+    painted crop corner of the raster matrix stays unseen."""
+    size, ay = geo
+    P, _, _ = EC.authored_world(size, ay)
+    crop = np.ones((P.crop, P.crop), np.uint8)
+    crop[0, 0] = 2
+    step = 1.0 if size < 256 else 3.0
+    angles = [-90.0 + step * i for i in range(int(360 / step))]
+    for d in (45.0, 135.0, 225.0, -45.0):
+        angles += [d + o for o in (0.0, 0.01, -0.01, 0.1, -0.1, 0.5, -0.5)]
+    for a in angles:
+        out = raster_ref.rotate_compose(P, crop, EC.yaw_of_angle(np.float32(a)), reset=False)
+        assert np.all(out == 1), (geo, a, np.unique(out))
+        tiles = EC.raster_classes(P, P.map_w / 2.0, P.map_h / 2.0, EC.yaw_of_angle(np.float32(a)))
+        assert all(t["fast"] and not t["outside"] and not t["clipped"] for t in tiles), (geo, a)
+
+
+def test_many_actor_case_oracle_equals_numpy():
+    P, padded, caps, recs, layout, acts = EC.many_actor_batch()
+    orc = O.Oracle(P, padded, caps.c(), layout.record_bytes)
+    frame = np.zeros((P.size, P.size), np.uint8)
+    seen = collections.Counter()
+    for e in range(len(recs)):
+        _, ref = _step_and_restate(P, padded, layout, orc, recs[e], acts[0, e], frame)
+        assert np.array_equal(frame, ref), (e, np.argwhere(frame != ref)[:5])
+        seen.update(dict(zip(*np.unique(frame, return_counts=True))))
+    # 70 vehicles of 16 texels: far more vehicle texels than 64 actors could paint are in view
+    assert seen[3] / len(recs) > 16 * 30 and seen[4] > 0
+
+
+@pytest.mark.parametrize("caps", [EC.CAPS_EGO8, EC.CAPS_EGO16], ids=["ego8", "ego16"])
+def test_long_routes_consume_targets_in_every_word(caps):
+    P, padded, caps, recs, layout, acts, n_place = EC.long_route_batch(caps)
+    orc = O.Oracle(P, padded, caps.c(), layout.record_bytes)
+    n = len(recs)
+    views = [LY.RecordView(recs[e], layout) for e in range(n)]
+    assert sorted({v.i("NROUTE") for v in views}) == list(EC.LONG_ROUTE_LENGTHS)
+    vis0 = np.stack([v.vis.copy() for v in views])
+    tidx0 = np.array([v.i("TIDX") for v in views])
+    frame = np.zeros((P.size, P.size), np.uint8)
+    for e in range(n_place):  # one step: the placement's own target is taken, in its word
+        _, ref = _step_and_restate(P, padded, layout, orc, recs[e], acts[0, e], frame)
+        assert np.array_equal(frame, ref), e
+    taken = np.stack([v.vis for v in views[:n_place]]) ^ vis0[:n_place]
+    for w in range(4):
+        assert np.count_nonzero(taken[:, w]) >= 3, (w, "no placement consumed a target of this word")
+    for t in range(EC.DRIVE_STEPS):
+        for e in range(n_place, n):
+            orc.step_one(recs[e], np.ascontiguousarray(acts[t, e]), None)
+    crossed = set()
+    for e in range(n_place, n):
+        gone = views[e].vis ^ vis0[e]
+        words = [w for w in range(4) if gone[w]]
+        assert words, (e, "a drive env consumed no target")
+        crossed.update((w, w + 1) for w in words if w + 1 in words)
+        assert views[e].i("TIDX") > tidx0[e]
+        crossed.update(("tidx", b) for b in (32, 64, 96) if tidx0[e] < b <= views[e].i("TIDX"))
+    assert crossed >= {(0, 1), (1, 2), (2, 3), ("tidx", 32), ("tidx", 64), ("tidx", 96)}, crossed
+
+
+def _angles_close(a, b, tol=1e-9):
+    d = np.remainder(np.asarray(a) - np.asarray(b) + np.pi, 2 * np.pi) - np.pi
+    return bool(np.all(np.abs(d) <= tol * (1 + np.abs(b))))
+
+
+@pytest.mark.parametrize("caps", EC.CAPS_RETREAT, ids=["slots32", "slots48", "slots96"])
+def test_retreat_routes_equal_host_smoothing(caps):
+    """Every retreat's rebuilt route against routes.smooth_and_compute (the host
+    smoothing test_oracle_golden pins to the reference) of
+    [pos] + initial_route[:cur + 1][::-1]."""
+    P, padded, caps, recs, layout, acts, cases = EC.retreat_batch(caps)
+    orc = O.Oracle(P, padded, caps.c(), layout.record_bytes)
+    views = [LY.RecordView(recs[e], layout) for e in range(len(recs))]
+    raw = {(e, s): EC.retreat_raw_route(views[e], s, cur) for e, cs in enumerate(cases) for s, cur, _ in cs}
+    for e in range(len(recs)):
+        orc.step_one(recs[e], np.ascontiguousarray(acts[0, e]), None)
+    nroutes, dedup = [], 0
+    for e, cs in enumerate(cases):
+        for s, cur, on in cs:
+            v = views[e]
+            assert v.ai[LY.AI["BSTATE"], s] == LY.BSTATE["retreating"], (e, s)
+            px, py = raw[(e, s)]
+            cx, cy, cyaw, _, _ = routes.smooth_and_compute(px, py, window=11, poly=3)
+            m = int(v.ai[LY.AI["NROUTE"], s])
+            assert m == len(cx) and v.ai[LY.AI["NRX"], s] == cur + 2, (e, s, m, len(cx))
+            assert np.allclose(v.acx[s, :m], cx, rtol=1e-9, atol=1e-9), (e, s, "acx")
+            assert np.allclose(v.acy[s, :m], cy, rtol=1e-9, atol=1e-9), (e, s, "acy")
+            assert _angles_close(v.acyaw[s, :m], cyaw), (e, s, "acyaw")
+            assert np.array_equal(v.arx[s, :cur + 2], px) and np.array_equal(v.ary[s, :cur + 2], py)
+            if e > 0:
+                nroutes.append(m)
+                dedup += m < cur + 2 and cur > 0
+    assert sorted(set(nroutes)) == list(range(2, 14)) + [32, 63, 64], sorted(set(nroutes))
+    assert sorted(int(views[0].ai[LY.AI["NROUTE"], s]) for s, _, _ in cases[0]) == sorted(
+        [2, 2] + list(range(3, 14)) + [32, 63, 64])
+    assert dedup == 1  # RETREAT_DEDUP: NRX 6, NROUTE 5
+    v = views[-1]
+    assert (v.ai[LY.AI["NRX"], 0], v.ai[LY.AI["NROUTE"], 0]) == (6, 5)
+    for t in range(1, EC.RETREAT_STEPS):
+        for e in range(len(recs)):
+            orc.step_one(recs[e], np.ascontiguousarray(acts[t, e]), None)
+    states = [int(views[e].ai[LY.AI["BSTATE"], s]) for e, cs in enumerate(cases) for s, _, _ in cs]
+    assert states.count(LY.BSTATE["retreated"]) >= 10 and states.count(LY.BSTATE["retreating"]) >= 3, states

@@ -161,18 +161,25 @@ def error_flags(ctx):
 
 def run_parity(kinds, n_envs, steps, size=128, profile="discrete9_v1", reward="carl_base_v1", seed0=0, anchor_y=0.5,
                act_seed=1234, edit=None, fov=False, caps=CAPS_FULL, options=None, acts=None, on_step=None,
-               stats=False):
+               stats=False, recs=None, world_=None):
     """Every env of a small batch stepped on the device and by the oracle, compared
-    whole after each step. acts: an explicit (steps, n[, 3]) action array instead of
-    the seeded stream; on_step(t, views, causes): sees the oracle's records after
+    whole after each step. recs (with world_ = (P, padded map) and caps): authored
+    records (tests/edge_cases.py) instead of the scene builder's; acts: an
+    explicit (steps, n[, 3]) action array instead of the seeded stream; on_step(t, views, causes): sees the oracle's records after
     each step (branch-coverage probes); stats: with the device episode statistics
     on (EpisodeStatsOn), the headline's k_ego variant."""
-    cfg, P, padded, layout, builder = world(size, profile, reward, anchor_y, caps=caps)
-    if options is None:
-        recs, _ = build_records(builder, n_envs, kinds, seed0=seed0)
-    else:  # explicit scene options (e.g. more vehicles than the difficulty presets)
-        recs, _ = builder.build_many([seed0 + i for i in range(n_envs)],
-                                     lambda k, s: dict(options[k % len(options)], scene_seed=s))
+    if recs is not None:  # authored records: no scene generator (size 64 has none that works)
+        P, padded = world_
+        layout = LY.Layout.make(caps)
+        recs = recs.copy()
+        assert recs.shape == (n_envs, layout.record_bytes) and edit is None
+    else:
+        cfg, P, padded, layout, builder = world(size, profile, reward, anchor_y, caps=caps)
+        if options is None:
+            recs, _ = build_records(builder, n_envs, kinds, seed0=seed0)
+        else:  # explicit scene options (e.g. more vehicles than the difficulty presets)
+            recs, _ = builder.build_many([seed0 + i for i in range(n_envs)],
+                                         lambda k, s: dict(options[k % len(options)], scene_seed=s))
     if edit is not None:  # hand-made states on top of the seeded scenes
         edit(recs, layout, P)
     dw = DevWorld(P, padded, caps)
@@ -375,12 +382,28 @@ def test_bank_reset_and_wrapper_expansion():
     assert np.array_equal(rgb.cpu().numpy(), PALETTE[ring_h[head].numpy()])
 
 
+def _authored64(n, first=0):
+    """n authored size-64 records (tests/edge_cases.py raster matrix, every 15th
+    case from `first`: the scene generator mostly cannot build size-64 scenes)."""
+    import edge_cases as EC
+    P, padded, caps, recs, layout, _ = EC.raster_batch(64, 0.5)
+    return P, padded, caps, np.ascontiguousarray(recs[first::15][:n])
+
+
 def test_reset_from_cached_bank_frames_matches_render():
     cfg, P, padded, layout, builder = world()
     n, B, F = 48, 9, 4
     recs, _ = build_records(builder, n, ["rt_medium_v1"], seed0=1300)
     bank, _ = build_records(builder, B, ["rt_hard_v1", "jaywalk", "lead_brake"], seed0=1900)
-    dw = DevWorld(P, padded, CAPS_FULL)
+    _cached_bank_frames_match_render(P, padded, CAPS_FULL, recs, bank, F)
+    # size 64 (k_bank_frames<1>, k_reset<1> into a 4-slot ring), authored records
+    P, padded, caps, recs = _authored64(n)
+    _cached_bank_frames_match_render(P, padded, caps, recs, _authored64(B, first=7)[3], F)
+
+
+def _cached_bank_frames_match_render(P, padded, caps, recs, bank, F):
+    n, B = len(recs), len(bank)
+    dw = DevWorld(P, padded, caps)
     L = lib()
     S = P.size
     d_bank = torch.from_numpy(bank.copy()).cuda()
@@ -403,6 +426,14 @@ def test_reset_from_cached_bank_frames_matches_render():
         outs.append((d_recs.cpu().numpy(), ring.cpu().numpy()))
     assert np.array_equal(outs[0][0], outs[1][0])
     assert np.array_equal(outs[0][1], outs[1][1])
+    # and the ring of a reset env is the oracle's reset frame of its bank row (second call: b = (e + 5) % B)
+    orc = O.Oracle(P, padded, caps.c(), LY.Layout.make(caps).record_bytes)
+    f = np.zeros((S, S), np.uint8)
+    for e in range(0, n, 5):
+        if e % 4 != 1:
+            orc.reset_obs(bank[(e + 5) % B].copy(), f)
+            for s in range(F):
+                assert np.array_equal(outs[1][1][s, e], f), (S, e, s)
 
 
 def test_vector_env_surface_and_partial_reset():
@@ -435,12 +466,17 @@ def test_vector_env_surface_and_partial_reset():
 
 def test_profile_raster_rerenders_the_step():
     """cbev_profile_raster (bench.py's burst-timed roofline) re-renders the frames
-    the preceding split step wrote, for traffic scenes at both sizes."""
-    for size, kinds in ((128, ["rt_hard_v1"]), (256, ["mix3"])):
-        cfg, P, padded, layout, builder = world(size, "discrete9_v1", "carl_base_v1", 0.5)
+    the preceding split step wrote, for traffic scenes at sizes 128 and 256 and
+    for authored painted scenes at size 64."""
+    for size, kinds in ((128, ["rt_hard_v1"]), (256, ["mix3"]), (64, None)):
         n = 48
-        recs, _ = build_records(builder, n, kinds, seed0=7)
-        dw = DevWorld(P, padded, CAPS_FULL)
+        if kinds is None:
+            P, padded, caps, recs = _authored64(n)
+        else:
+            cfg, P, padded, layout, builder = world(size, "discrete9_v1", "carl_base_v1", 0.5)
+            recs, _ = build_records(builder, n, kinds, seed0=7)
+            caps = CAPS_FULL
+        dw = DevWorld(P, padded, caps)
         L = lib()
         S = P.size
         d_recs = torch.from_numpy(recs.copy()).cuda()
