@@ -2078,32 +2078,8 @@ __device__ __forceinline__ void raster_reset_frame(const KArgs& K, int row, int 
   }
 }
 
-// One (env, tile) per workgroup; register target from the LDS-limited residency
-// (Tiles::wgs_per_cu workgroups of 4 waves per CU = waves per SIMD). The raster
-// kernels declare no static LDS: the gathers address the LDS absolutely.
+// k_raster (one (env, tile) per workgroup) follows k_ego, whose tail it can carry
 constexpr int kRasterNT = 256;  // k_raster's workgroup size
-template <int G>
-__global__ __launch_bounds__(kRasterNT)
-__attribute__((amdgpu_waves_per_eu(Tiles<G>::wgs_per_cu * kRasterNT / 256 > 8 ? 8 : Tiles<G>::wgs_per_cu * kRasterNT / 256)))
-void k_raster(KArgs K, uint8_t* __restrict__ recs, int n, uint8_t* __restrict__ frames) {
-  extern __shared__ __align__(16) uint8_t lds[];
-  CBEV_STAMP(2, 0);
-  int e, t;
-  xcd_tile_of_wg(blockIdx.x, n, Tiles<G>::T, &e, &t);
-  if (e >= n) return;
-  const int64_t SS = (int64_t)K.P.size * K.P.size;
-  const DRec r = bind_rec(recs + (int64_t)e * K.L.record_bytes, K.L, K.C);
-  const RasterJob J = raster_job<false, G>(K, r);
-  // a reset k_ego folded into this step (KArgs::rmask; RS_FAST bits 1.. = its bank
-  // row + 1): this tile of the bank frame into every ring slot but the one this
-  // step renders (FrameStackObservation's reset padding), by the few reset
-  // items only, after the render (loads and stores there: no register is held
-  // across the render for it)
-  const int row = K.rbank_frames != nullptr && K.rn_frames > 1 ? (r.hi[CBEV_HI_RS_FAST] >> 1) - 1 : -1;
-  raster_tile<G, true, kRasterNT>(K, r, J, t, frames + e * SS, 1, 0, lds);
-  if (row >= 0) raster_reset_frame<G>(K, row, e, t);
-  CBEV_STAMP(2, 3);
-}
 
 // BaseMap.reset's observation (theta = 0, nothing painted, world.py:92-100) of
 // one record by a 256-thread workgroup, tile by tile, into `nout` frames
@@ -2902,26 +2878,113 @@ __device__ __forceinline__ void ego_restage(uint8_t* lds, Src src, uint64_t bits
 //   S6  the collision + reward + termination chain, one thread per env
 //       (collide_env)
 //   S7  HD, HI and the vis group back to the records
-// k_raster reads only what this kernel wrote (RS_* set-up, poses, vis_draw),
-// so collision no longer has to wait for the frame.
-__global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, int ne, int st_rb, int st_n0, int st_n,
-                                             int st_raw_x, KArgs K,
-                                             const void* __restrict__ actions, double* __restrict__ reward_out,
-                                             uint8_t* __restrict__ term_out, uint8_t* __restrict__ trunc_out,
-                                             int32_t* __restrict__ cause_out, float* __restrict__ info_out) {
-  extern __shared__ __align__(16) uint8_t lds[];
+// k_raster reads only what S0-S4 wrote (RS_* set-up, poses, vis_draw), so
+// collision no longer has to wait for the frame, and S5-S7 need not come before
+// it either. The body is two device functions cut at the S4 / S5 barrier:
+//   ego_front  S0-S4 (a folded reset included)
+//   ego_tail   S5-S7
+// k_ego runs both in one workgroup (WHOLE: the tail takes the front's LDS and
+// registers, one write-back at the end). The split step (cbev_set_split_step)
+// launches k_ego_head = the front with its own write-back, and the tail rides
+// in k_raster's launch as its leading workgroups (its own stage-in from the
+// records the head updated, the cheap S4 pieces it needs computed again), where
+// its latency-bound float64 chains run beside the render instead of before it.
+
+// S5's route points per thread loaded ahead
+constexpr int S5_PF = 4;
+// What the tail takes from S0-S4 in registers: handed over by the front in
+// k_ego, loaded by the tail itself in k_raster's tail role.
+struct EgoCarry {
+  uint64_t rbits;                 // the folded reset's envs (EgoReset::bits; 0 in the tail role: already applied)
+  uint32_t tc0;                   // thread k < ne: env e0 + k's terminations so far
+  double t5x[S5_PF], t5y[S5_PF];  // S5's first route points (env tid / tpe, points sub, sub + tpe, ...)
+  double pax, pay, payaw, pav;    // S5's first (env, actor) pair of this thread
+  int pasz;
+  double spx, spy;                // S6's Stanley set point (wave 0 lane k = S6's thread of env k)
+  uint4 rest_v;                   // k_ego: a reset env's piece held for the write-back (rest_k < 0: none)
+  int rest_k, rest_o;
+};
+// LDS of a k_ego workgroup: [ne] record slots, then (nslot == 2, contexts the
+// reset can fold into: no actor slots) [ne] bank-row slots, then the collision
+// scratch. The tail role has nslot == 1 and uses neither best nor rrow.
+struct EgoLds {
+  uint8_t* scr;  // [ne] collision scratch (from S4; the folded reset's mask bits before)
+  HeroPre* pre;  // [ne]
+  int* best;     // [ne] target search result
+  int* rrow;     // [ne] a folded reset's bank row per env
+};
+__device__ __forceinline__ EgoLds ego_lds(uint8_t* lds, int nslot, int ne, const EgoPack& pk,
+                                          const CollScratchLayout& SL) {
+  EgoLds o;
+  o.scr = lds + nslot * ne * pk.bytes;
+  o.pre = (HeroPre*)(o.scr + ne * SL.bytes);
+  o.best = (int*)(o.pre + ne);
+  o.rrow = o.best + ne;
+  return o;
+}
+__device__ __forceinline__ void ego_t5_load(EgoCarry& C, const KArgs& K, const DRec& g, int ne) {
+  const int tpe5 = 256 / ne, k5 = threadIdx.x / tpe5, sub5 = threadIdx.x - k5 * tpe5;
+#pragma unroll
+  for (int j = 0; j < S5_PF; ++j) {
+    const int i = min(sub5 + j * tpe5, K.C.route_cap - 1);
+    C.t5x[j] = g.cx[i];
+    C.t5y[j] = g.cy[i];
+  }
+}
+// the (env, actor) pair of S5 this thread takes first
+__device__ __forceinline__ void ego_actor_load(EgoCarry& C, const DRec& g, int a) {
+  C.pax = RAD(g, CBEV_AD_X, a);
+  C.pay = RAD(g, CBEV_AD_Y, a);
+  C.payaw = RAD(g, CBEV_AD_YAW, a);
+  C.pav = RAD(g, CBEV_AD_V, a);
+  C.pasz = RAI(g, CBEV_AI_SIZE, a);
+}
+// S4's collision prologue of one env (one lane): S6's set point, the ego tile
+// load, the hero rect and the scratch S5 accumulates into; DRAW: with the vis
+// words the observation will draw (vis_draw <- vis, the front's)
+template <bool DRAW>
+__device__ __forceinline__ void ego_coll_prologue(const KArgs& K, const DRec& r, uint8_t* sk,
+                                                  const CollScratchLayout& SL, EgoCarry& C) {
+  const cbev_params& P = K.P;
+  const int tidx = r.hi[CBEV_HI_TIDX];  // after S3 (scene_info, scene.py:206-225)
+  C.spx = r.cx[tidx];
+  C.spy = r.cy[tidx];
+  const double x = r.hd[CBEV_HD_X], y = r.hd[CBEV_HD_Y];
+  const int tx = (int)d_clip(rint(x), 0, P.map_w - 1), ty = (int)d_clip(rint(y), 0, P.map_h - 1);
+  const int tile = d_map_texel(K, tx + P.pad, ty + P.pad);  // world.py:159-165
+  int* I = (int*)(sk + SL.ints);
+  I[CS_TGT_LAST] = -1;
+  I[CS_ACT_LAST] = -1;
+  I[CS_NAS] = 0;
+  I[3] = d_rect_lo(x, P.pad, P.hero_w);
+  I[4] = d_rect_lo(y, P.pad, P.hero_w);
+  uint32_t* hitw = (uint32_t*)(sk + SL.hitw);
+  for (int w = 0; w < K.L.vis_words; ++w) {
+    hitw[w] = 0;
+    if (DRAW) r.vis_draw[w] = r.vis[w];
+  }
+  I[CS_TILE] = tile;
+}
+
+// S0-S4 for the workgroup's envs. WHOLE (k_ego): the tail follows in the same
+// workgroup and gets its registers in C; returns false when the workgroup has no
+// env. Otherwise (k_ego_head) the records are written back here: HD, HI, the
+// vis group, and a reset env's remaining pieces.
+template <bool WHOLE>
+__device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ recs, int n, int ne, int st_rb,
+                                          int st_n0, int st_n, int st_raw_x, const KArgs& K,
+                                          const void* __restrict__ actions, EgoCarry& C) {
   CBEV_STAMP(0, 0);
   const int e0 = staged_env0(blockIdx.x, ne, n);
   const int ne_eff = min(ne, n - e0);
   const EgoPack pk = ego_pack(K.L);
-  // LDS: [ne] record slots, then (contexts the reset can fold into: no actor
-  // slots) [ne] bank-row slots, then the collision scratch
   const int nslot = K.C.actor_cap == 0 ? 2 : 1;
-  uint8_t* scr = lds + nslot * ne * pk.bytes;  // [ne] collision scratch (from S4; the folded reset's mask bits before)
   const CollScratchLayout SL = coll_scratch_layout(K.C, K.L.vis_words);
-  HeroPre* pre = (HeroPre*)(scr + ne * SL.bytes);  // [ne]
-  int* best = (int*)(pre + ne);                   // [ne] target search result
-  int* rrow = best + ne;                          // [ne] a folded reset's bank row per env
+  const EgoLds M = ego_lds(lds, nslot, ne, pk, SL);
+  uint8_t* const scr = M.scr;
+  HeroPre* const pre = M.pre;
+  int* const best = M.best;
+  int* const rrow = M.rrow;
   // S0: the staging first (it depends on nothing loaded, and its scalars are
   // preloaded), then the action loads and the actor prefetch, whose latency
   // overlaps the staging's. With a folded reset the records are staged
@@ -2964,23 +3027,15 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
   // S5's targets (env tid / tpe, points sub, sub + tpe, ...): the first S5_PF of
   // a thread's route points, loaded now; the Stanley set point of S6's thread
   // (tid < ne) is loaded in S4 once S3 has moved the target index
-  constexpr int S5_PF = 4;
-  const int tpe5 = 256 / ne, k5 = tid / tpe5, sub5 = tid - k5 * tpe5;
-  double t5x[S5_PF], t5y[S5_PF];
-  auto t5_load = [&](const DRec& g) {
-#pragma unroll
-    for (int j = 0; j < S5_PF; ++j) {
-      const int i = min(sub5 + j * tpe5, K.C.route_cap - 1);
-      t5x[j] = g.cx[i];
-      t5y[j] = g.cy[i];
-    }
-  };
-  if (k5 < ne_eff) t5_load(bind_rec(src_rec(k5), K.L, K.C));
+  const int tpe5 = 256 / ne, k5 = tid / tpe5;
+  if (WHOLE && k5 < ne_eff) ego_t5_load(C, K, bind_rec(src_rec(k5), K.L, K.C), ne);
   // the env's terminations so far (lane k of wave 0 = env e0 + k, also S6's
   // thread): the folded reset's bank row, and counted up at S6 on termination
   const uint32_t tc0 = tid < ne_eff ? K.tcount[e0 + tid] : 0u;
+  C.tc0 = tc0;
   EgoReset R{0ull};
   if (K.rmask != nullptr) R = ego_reset_take(K, e0, ne_eff, tc0, (int*)scr, rrow);
+  C.rbits = R.bits;
   auto src = [&](int k) -> uint8_t* {
     if (R.bits != 0ull && ((R.bits >> k) & 1ull))
       return (uint8_t*)K.rbank + (int64_t)rrow[k] * st_rb;
@@ -2992,14 +3047,13 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
       s2g = bind_rec(src(s2k), K.L, K.C);
       s2_load();
     }
-    if (k5 < ne_eff && ((R.bits >> k5) & 1ull)) t5_load(bind_rec(src(k5), K.L, K.C));
+    if (WHOLE && k5 < ne_eff && ((R.bits >> k5) & 1ull)) ego_t5_load(C, K, bind_rec(src(k5), K.L, K.C), ne);
   }
   // env k's staged ranges: its record slot, or its bank-row slot when the folded reset takes it
   auto slot = [&](int k) -> uint8_t* { return lds + ((R.bits >> k) & 1ull ? ne + k : k) * pk.bytes; };
   CBEV_STAMP(3, 0);
-  const cbev_params& P = K.P;
   const int64_t rb = K.L.record_bytes;
-  if (ne_eff <= 0) return;
+  if (ne_eff <= 0) return false;
   // the folded reset's record ranges k_ego does not write back ([cx, vis) and
   // past the vis group), bank row -> record: one 16-byte piece per thread
   // loaded now and stored at S7 (more pieces than threads: copied at S7)
@@ -3019,7 +3073,6 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
     asm volatile("" ::"v"(rest_v.x), "v"(rest_v.y), "v"(rest_v.z), "v"(rest_v.w));  // issued here, not sunk to S7
   }
   auto rec = [&](int k) { return bind_ego(slot(k), src(k), K, pk); };
-  if (blockIdx.x == 0 && tid == 0 && K.ep_count_next != nullptr) *K.ep_count_next = 0;
   // S1 on the staging waves once their LDS-DMA is issued (they would otherwise
   // idle until the barrier; S2 on waves 0 and 1 then starts as soon as its own
   // loads land): the actions, and from the record's yaw and speed cos / sin of
@@ -3041,16 +3094,11 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
   // the (env, actor) pair of S5 this thread takes first: its actor's fields are
   // loaded now, in flight under S0-S4 (slots past NACT hold zeros and are skipped)
   const int A = K.C.actor_cap;
-  double pax = 0.0, pay = 0.0, payaw = 0.0, pav = 0.0;
-  int pasz = 0;
-  if (tid < ne_eff * A) {
-    const int k = tid / A, a = tid - k * A;
-    const DRec g = bind_rec(src(k), K.L, K.C);
-    pax = RAD(g, CBEV_AD_X, a);
-    pay = RAD(g, CBEV_AD_Y, a);
-    payaw = RAD(g, CBEV_AD_YAW, a);
-    pav = RAD(g, CBEV_AD_V, a);
-    pasz = RAI(g, CBEV_AI_SIZE, a);
+  C.pax = C.pay = C.payaw = C.pav = 0.0;
+  C.pasz = 0;
+  if (WHOLE && tid < ne_eff * A) {
+    const int k = tid / A;
+    ego_actor_load(C, bind_rec(src(k), K.L, K.C), tid - k * A);
   }
   CBEV_STAMP(3, 1);
   // S2: Controller.calc_target_index (stanley_controller.py:51-62),
@@ -3128,7 +3176,7 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
   }
   __syncthreads();
   // S4
-  double s6spx = 0.0, s6spy = 0.0;  // S6's set point (wave 0 lane k = S6's thread of env k)
+  C.spx = C.spy = 0.0;
   if (lane < ne_eff) {
     if (wave == 1) {
       hero_env_comfort(rec(lane));
@@ -3138,33 +3186,147 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
       // a folded reset's bank row for k_raster (the reset frame into the other ring
       // slots), beside the fast bit it reads anyway: RS_FAST bits 1.. = row + 1
       if ((R.bits >> lane) & 1ull) rr.hi[CBEV_HI_RS_FAST] |= (rrow[lane] + 1) << 1;
-    } else if (wave == 3) {  // the updated yaw's cos / sin for the actors' TTCs (S5)
+    } else if (WHOLE && wave == 3) {  // the updated yaw's cos / sin for the actors' TTCs (S5)
       const double yaw = ((const double*)(slot(lane) + K.L.hd))[CBEV_HD_YAW];
       d_sincos(yaw, &pre[lane].syaw, &pre[lane].cyaw);
     } else if (wave == 0) {
       const DRec r = rec(lane);
-      const int tidx = r.hi[CBEV_HI_TIDX];  // after S3 (scene_info, scene.py:206-225)
-      s6spx = r.cx[tidx];
-      s6spy = r.cy[tidx];
-      const double x = r.hd[CBEV_HD_X], y = r.hd[CBEV_HD_Y];
-      const int tx = (int)d_clip(rint(x), 0, P.map_w - 1), ty = (int)d_clip(rint(y), 0, P.map_h - 1);
-      const int tile = d_map_texel(K, tx + P.pad, ty + P.pad);  // world.py:159-165
-      int* I = (int*)(scr + lane * SL.bytes + SL.ints);
-      I[CS_TGT_LAST] = -1;
-      I[CS_ACT_LAST] = -1;
-      I[CS_NAS] = 0;
-      I[3] = d_rect_lo(x, P.pad, P.hero_w);
-      I[4] = d_rect_lo(y, P.pad, P.hero_w);
-      uint32_t* hitw = (uint32_t*)(scr + lane * SL.bytes + SL.hitw);
-      for (int w = 0; w < K.L.vis_words; ++w) {
-        hitw[w] = 0;
-        r.vis_draw[w] = r.vis[w];
+      if (WHOLE) {
+        ego_coll_prologue<true>(K, r, scr + lane * SL.bytes, SL, C);
+      } else {
+        for (int w = 0; w < K.L.vis_words; ++w) r.vis_draw[w] = r.vis[w];
       }
-      I[CS_TILE] = tile;
     }
   }
   __syncthreads();
   CBEV_STAMP(0, 3);
+  if (WHOLE) {  // written back after the tail
+    C.rest_v = rest_v;
+    C.rest_k = rest_k;
+    C.rest_o = rest_o;
+    return true;
+  }
+  // the head's write-back: all the raster reads, and the records the tail stages from
+  ego_stage_out(slot, recs, e0, ne_eff, K, pk);
+  if (rest_k >= 0) *(uint4*)(recs + (int64_t)(e0 + rest_k) * rb + rest_o) = rest_v;
+  for (int q = threadIdx.x + 256; q < nres * rpp; q += 256) {
+    int k, o;
+    rest_piece(q, &k, &o);
+    *(uint4*)(recs + (int64_t)(e0 + k) * rb + o) = *(const uint4*)(src(k) + o);
+  }
+  return true;
+}
+
+// ---- the tail's write-back beside the raster. In k_raster's tail role it runs
+// while the launch's other workgroups read the same records, so it stores to no
+// dword the raster reads. The raster's record inputs (raster_job,
+// raster_paint_fetch, paint_tile, crop_background, k_raster):
+//   HI   NROUTE, NACT, NVEH, NTL, RS_XMIN .. RS_FAST (kRasterHi)
+//   the route cx / cy, vis_draw, the actors' AD_X / AD_Y / AI_SIZE, the traffic
+//   lights' ints
+// and nothing of HD. The tail changes HD, the HI words of kTailHi and vis. HD
+// goes back whole (16-byte pieces: HI starts 64-byte aligned after it); a
+// 16-byte piece of HI goes back whole when it holds no raster input, else the
+// words the tail changes one by one; vis (vis_draw follows it without padding,
+// so a piece can straddle both) word by word.
+#define CBEV_HI_BIT(n) (1ull << CBEV_HI_##n)
+constexpr uint64_t kRasterHi = CBEV_HI_BIT(NROUTE) | CBEV_HI_BIT(NACT) | CBEV_HI_BIT(NVEH) | CBEV_HI_BIT(NTL) |
+                               ((2ull << CBEV_HI_RS_FAST) - (1ull << CBEV_HI_RS_XMIN));
+constexpr uint64_t kTailHi = CBEV_HI_BIT(S_PREV_VALID) | CBEV_HI_BIT(KSTEPS) | CBEV_HI_BIT(OFFROAD) |
+                             CBEV_HI_BIT(CAUSE) | CBEV_HI_BIT(TERM) | CBEV_HI_BIT(TRUNC) | CBEV_HI_BIT(TILE) |
+                             CBEV_HI_BIT(COLLIDED) | CBEV_HI_BIT(ACTOR_ID) | CBEV_HI_BIT(EP_LEN) | CBEV_HI_BIT(STEP) |
+                             CBEV_HI_BIT(NACTSTATE);
+static_assert(CBEV_HI_COUNT <= 64 && (kRasterHi & kTailHi) == 0, "the tail writes a HI word the raster reads");
+static_assert(CBEV_HI_RS_FAST == CBEV_HI_RS_R90 + CBEV_RS_WORDS && CBEV_HI_RS_R90 == CBEV_HI_RS_XMIN + 2,
+              "kRasterHi: RS_XMIN .. RS_FAST are consecutive");
+__device__ __forceinline__ void ego_tail_out(const uint8_t* lds, uint8_t* __restrict__ recs, int e0, int ne,
+                                             const KArgs& K, const EgoPack& p) {
+  const int nhd = (int)((K.L.hi - K.L.hd) / 16), nhi = (CBEV_HI_COUNT + 3) / 4;
+  const int nout = nhd + nhi + K.L.vis_words;
+  const int64_t rb = K.L.record_bytes;
+  for (int q = threadIdx.x; q < ne * nout; q += 256) {
+    const int k = q / nout, j = q - k * nout;
+    uint8_t* g = recs + (int64_t)(e0 + k) * rb;
+    const uint8_t* l = lds + k * p.bytes;  // the first range sits at the record's offsets
+    if (j < nhd) {
+      const int o = (int)K.L.hd + 16 * j;
+      *(uint4*)(g + o) = *(const uint4*)(l + o);
+    } else if (j < nhd + nhi) {
+      const int pc = j - nhd, o = (int)K.L.hi + 16 * pc;
+      const uint32_t tm = (uint32_t)(kTailHi >> (4 * pc)) & 15u, rm = (uint32_t)(kRasterHi >> (4 * pc)) & 15u;
+      if (tm != 0u && rm == 0u) {
+        *(uint4*)(g + o) = *(const uint4*)(l + o);
+      } else {
+        for (int b = 0; b < 4; ++b)
+          if ((tm >> b) & 1u) *(uint32_t*)(g + o + 4 * b) = *(const uint32_t*)(l + o + 4 * b);
+      }
+    } else {
+      const int w = j - nhd - nhi;
+      *(uint32_t*)(g + K.L.vis + 4 * w) = *(const uint32_t*)(l + 16 * p.n0 + (K.L.vis - K.L.raw_x) + 4 * w);
+    }
+  }
+}
+
+// S5-S7 for the workgroup's envs. WHOLE (k_ego): after ego_front in the same
+// workgroup, on its LDS and C. Otherwise k_raster's tail role: the records are
+// the head's (a folded reset already applied: no bank slots), staged in here.
+template <bool WHOLE>
+__device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ recs, int n, int ne, int st_rb,
+                                         int st_n0, int st_n, int st_raw_x, const KArgs& K,
+                                         double* __restrict__ reward_out, uint8_t* __restrict__ term_out,
+                                         uint8_t* __restrict__ trunc_out, int32_t* __restrict__ cause_out,
+                                         float* __restrict__ info_out, EgoCarry& C) {
+  const int e0 = staged_env0(blockIdx.x, ne, n);
+  const int ne_eff = min(ne, n - e0);
+  if (ne_eff <= 0) return;
+  const EgoPack pk = ego_pack(K.L);
+  const int nslot = WHOLE && K.C.actor_cap == 0 ? 2 : 1;
+  const CollScratchLayout SL = coll_scratch_layout(K.C, K.L.vis_words);
+  const EgoLds M = ego_lds(lds, nslot, ne, pk, SL);
+  uint8_t* const scr = M.scr;
+  HeroPre* const pre = M.pre;
+  const int* const rrow = M.rrow;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const cbev_params& P = K.P;
+  const int64_t rb = K.L.record_bytes;
+  const int A = K.C.actor_cap;
+  const uint64_t rbits = WHOLE ? C.rbits : 0ull;
+  auto src = [&](int k) -> uint8_t* {
+    if (rbits != 0ull && ((rbits >> k) & 1ull))
+      return (uint8_t*)K.rbank + (int64_t)rrow[k] * st_rb;
+    return recs + (int64_t)(e0 + k) * st_rb;
+  };
+  auto slot = [&](int k) -> uint8_t* { return lds + ((rbits >> k) & 1ull ? ne + k : k) * pk.bytes; };
+  auto rec = [&](int k) { return bind_ego(slot(k), src(k), K, pk); };
+  if (blockIdx.x == 0 && tid == 0 && K.ep_count_next != nullptr) *K.ep_count_next = 0;
+  if (!WHOLE) {
+    // S0 again for the tail role: the staging (waves 2 and 3), then S5's
+    // prefetches, and under the staging the S4 pieces the tail needs, from the
+    // record in HBM (waves 0 and 1): the collision prologue, and the updated
+    // yaw's cos / sin for the actors' TTCs
+    ego_stage_in(lds, src, ne_eff, st_n0, st_n, st_raw_x);
+    const int tpe5 = 256 / ne, k5 = tid / tpe5;
+    if (k5 < ne_eff) ego_t5_load(C, K, bind_rec(src(k5), K.L, K.C), ne);
+    C.tc0 = tid < ne_eff ? K.tcount[e0 + tid] : 0u;
+    C.pax = C.pay = C.payaw = C.pav = 0.0;
+    C.pasz = 0;
+    if (tid < ne_eff * A) {
+      const int k = tid / A;
+      ego_actor_load(C, bind_rec(src(k), K.L, K.C), tid - k * A);
+    }
+    C.spx = C.spy = 0.0;
+    if (lane < ne_eff) {
+      const DRec g = bind_rec(src(lane), K.L, K.C);
+      if (wave == 0) {
+        ego_coll_prologue<false>(K, g, scr + lane * SL.bytes, SL, C);
+      } else if (wave == 1) {
+        d_sincos(g.hd[CBEV_HD_YAW], &pre[lane].syaw, &pre[lane].cyaw);
+      }
+    }
+    __syncthreads();  // the staging has landed; the prologue's scratch in LDS
+  }
+  const uint32_t tc0 = C.tc0;
   CBEV_STAMP(1, 0);
   // S5 (env k, element i) pairs: env k = tid / tpe, elements sub, sub + tpe, ...
   {
@@ -3237,7 +3399,7 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
         const int i = sub + j * tpe;
         if (i >= nt || !((r.vis[i >> 5] >> (i & 31)) & 1u)) continue;
         const int sz = (i < nt - 1) ? 2 : 4;
-        const int trx = d_rect_lo(t5x[j], P.pad, sz), try_ = d_rect_lo(t5y[j], P.pad, sz);
+        const int trx = d_rect_lo(C.t5x[j], P.pad, sz), try_ = d_rect_lo(C.t5y[j], P.pad, sz);
         if (hrx < trx + sz && hry < try_ + sz && hrx + hw > trx && hry + hw > try_) {
           atomicOr((uint32_t*)(sk + SL.hitw) + (i >> 5), 1u << (i & 31));
           atomicMax(&I[CS_TGT_LAST], i);
@@ -3265,8 +3427,8 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
       const int hrx = I[3], hry = I[4];
       const double x = r.hd[CBEV_HD_X], y = r.hd[CBEV_HD_Y], v = r.hd[CBEV_HD_V];
       const bool mine = q == tid;  // prefetched at S0
-      const int sz = mine ? pasz : RAI(r, CBEV_AI_SIZE, a);
-      const double ax = mine ? pax : RAD(r, CBEV_AD_X, a), ay = mine ? pay : RAD(r, CBEV_AD_Y, a);
+      const int sz = mine ? C.pasz : RAI(r, CBEV_AI_SIZE, a);
+      const double ax = mine ? C.pax : RAD(r, CBEV_AD_X, a), ay = mine ? C.pay : RAD(r, CBEV_AD_Y, a);
       const int arx = d_rect_lo(ax, P.pad, sz), ary = d_rect_lo(ay, P.pad, sz);
       if (hw > 0 && sz > 0 && hrx < arx + sz && hry < ary + sz && hrx + hw > arx && hry + hw > ary)
         atomicMax(&I[CS_ACT_LAST], a);
@@ -3279,7 +3441,7 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
         const double cyaw = pre[k].cyaw, syaw = pre[k].syaw;  // cos / sin of the updated yaw (S4)
         const double hvx_m = hv_m * cyaw, hvy_m = hv_m * syaw;
         const double hvx = v * cyaw, hvy = v * syaw;
-        const double av = mine ? pav : RAD(r, CBEV_AD_V, a), ayaw = mine ? payaw : RAD(r, CBEV_AD_YAW, a);
+        const double av = mine ? C.pav : RAD(r, CBEV_AD_V, a), ayaw = mine ? C.payaw : RAD(r, CBEV_AD_YAW, a);
         double say, cay;
         d_sincos(ayaw, &say, &cay);
         const double avx = av * cay, avy = av * say;
@@ -3308,22 +3470,121 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
   if (tid < ne_eff) {
     const DRec r = rec(tid);
     CollPre cp = coll_reduce_serial(scr + tid * SL.bytes, SL, r.hi[CBEV_HI_NACT], r.hi[CBEV_HI_NRAW]);
-    cp.spx = s6spx;  // tid < ne: wave 0, the lane that loaded them in S4
-    cp.spy = s6spy;
+    cp.spx = C.spx;  // tid < ne: wave 0, the lane that loaded them in S4
+    cp.spy = C.spy;
     collide_env(K, r, e0 + tid, cp, reward_out, term_out, trunc_out, cause_out, info_out);
     if (r.hi[CBEV_HI_TERM]) K.tcount[e0 + tid] = tc0 + 1u;  // the next reset's bank row moves on
   }
   __syncthreads();
   CBEV_STAMP(1, 2);
   // S7
+  if (!WHOLE) {
+    ego_tail_out(lds, recs, e0, ne_eff, K, pk);
+    CBEV_STAMP(1, 3);
+    return;
+  }
   ego_stage_out(slot, recs, e0, ne_eff, K, pk);
-  if (rest_k >= 0) *(uint4*)(recs + (int64_t)(e0 + rest_k) * rb + rest_o) = rest_v;
+  // a folded reset's remaining pieces (ego_front's rest_piece: more pieces than threads are copied here)
+  if (C.rest_k >= 0) *(uint4*)(recs + (int64_t)(e0 + C.rest_k) * rb + C.rest_o) = C.rest_v;
+  const int rsA = (int)((K.L.vis - K.L.cx) / 16), rsB0 = (int)(K.L.vis / 16) + pk.nvis;
+  const int rpp = rsA + (int)(rb / 16) - rsB0, nres = __popcll(rbits);
   for (int q = threadIdx.x + 256; q < nres * rpp; q += 256) {
-    int k, o;
-    rest_piece(q, &k, &o);
+    const int k = nth_set_bit(rbits, q / rpp), c = q % rpp;
+    const int o = c < rsA ? (int)K.L.cx + 16 * c : 16 * (rsB0 + c - rsA);
     *(uint4*)(recs + (int64_t)(e0 + k) * rb + o) = *(const uint4*)(src(k) + o);
   }
   CBEV_STAMP(1, 3);
+}
+
+__global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, int ne, int st_rb, int st_n0, int st_n,
+                                             int st_raw_x, KArgs K,
+                                             const void* __restrict__ actions, double* __restrict__ reward_out,
+                                             uint8_t* __restrict__ term_out, uint8_t* __restrict__ trunc_out,
+                                             int32_t* __restrict__ cause_out, float* __restrict__ info_out) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  EgoCarry C;
+  if (!ego_front<true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C)) return;
+  ego_tail<true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out, trunc_out, cause_out,
+                 info_out, C);
+}
+
+// The split step's first launch: the front alone. It reads the previous step's
+// term bytes as the folded reset's mask; this step's are written by the tail in
+// the next launch of the stream, so the mask is read before it is overwritten.
+__global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, int n, int ne, int st_rb, int st_n0,
+                                                  int st_n, int st_raw_x, KArgs K,
+                                                  const void* __restrict__ actions) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  EgoCarry C;
+  (void)ego_front<false>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C);
+}
+
+// k_ego's tail as k_raster's leading workgroups (cbev_set_split_step)
+struct TailArgs {
+  int ntail;  // workgroups of the tail role, a multiple of 8 (surplus ones exit); 0: none
+  int ne, rb, n0, np, raw_x;  // envs per tail workgroup; the staging scalars of k_ego
+  double* reward;
+  uint8_t* term;
+  uint8_t* trunc;
+  int32_t* cause;
+  float* info;
+};
+
+// One (env, tile) per workgroup; register target from the LDS-limited residency
+// (Tiles::wgs_per_cu workgroups of 4 waves per CU = waves per SIMD). The raster
+// kernels declare no static LDS: the gathers address the LDS absolutely.
+// The first T.ntail workgroups (dispatched first; G > 1 only: at 8 waves per
+// SIMD the tail would spill) run k_ego's tail on the same LDS size instead. No
+// workgroup waits for another: the head's launch has finished, the tail reads
+// nothing the raster writes, and writes nothing the raster reads
+// (ego_tail_out). ntail % 8 == 0 keeps w % 8, so the XCD placement, of both roles.
+// The arguments are one struct so that the tail role can read them where it
+// uses them, through the kernarg segment's pointer: as by-value arguments every
+// field either role uses is loaded in the kernel's entry block, and the tail's
+// many (the reward parameters) pushed the raster role into 96 SGPR spills there.
+struct RasterArgs {
+  KArgs K;
+  uint8_t* recs;
+  int n;
+  uint8_t* frames;
+  TailArgs T;
+};
+template <int G>
+__global__ __launch_bounds__(kRasterNT)
+__attribute__((amdgpu_waves_per_eu(Tiles<G>::wgs_per_cu * kRasterNT / 256 > 8 ? 8 : Tiles<G>::wgs_per_cu * kRasterNT / 256)))
+void k_raster(RasterArgs A) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  if constexpr (G > 1) {
+    if ((int)blockIdx.x < A.T.ntail) {
+      const RasterArgs M = *(const RasterArgs*)__builtin_amdgcn_kernarg_segment_ptr();  // loaded in this branch
+      const TailArgs& T = M.T;
+      EgoCarry C;
+      ego_tail<false>(lds, M.recs, M.n, T.ne, T.rb, T.n0, T.np, T.raw_x, M.K, T.reward, T.term, T.trunc, T.cause,
+                      T.info, C);
+      return;
+    }
+  }
+  const KArgs& K = A.K;
+  uint8_t* __restrict__ const recs = A.recs;
+  uint8_t* __restrict__ const frames = A.frames;
+  const int n = A.n;
+  const TailArgs& T = A.T;
+  CBEV_STAMP(2, 0);
+  int e, t;
+  xcd_tile_of_wg((int)blockIdx.x - T.ntail, n, Tiles<G>::T, &e, &t);
+  if (e >= n) return;
+  const int64_t SS = (int64_t)K.P.size * K.P.size;
+  const DRec r = bind_rec(recs + (int64_t)e * K.L.record_bytes, K.L, K.C);
+  const RasterJob J = raster_job<false, G>(K, r);
+  // a reset k_ego folded into this step (KArgs::rmask; RS_FAST bits 1.. = its bank
+  // row + 1): this tile of the bank frame into every ring slot but the one this
+  // step renders (FrameStackObservation's reset padding), by the few reset
+  // items only, after the render (loads and stores there: no register is held
+  // across the render for it)
+  const int row = K.rbank_frames != nullptr && K.rn_frames > 1 ? (r.hi[CBEV_HI_RS_FAST] >> 1) - 1 : -1;
+  raster_tile<G, true, kRasterNT>(K, r, J, t, frames + e * SS, 1, 0, lds);
+  if (row >= 0) raster_reset_frame<G>(K, row, e, t);
+  CBEV_STAMP(2, 3);
 }
 
 
@@ -3954,6 +4215,8 @@ struct cbev_ctx {
   int npitch;            // nibble-packed map pitch (bytes)
   int ego_ne;            // k_ego: envs per workgroup
   int ego_lb;            // k_ego: dynamic LDS bytes per workgroup
+  int tail_ne;           // k_raster's tail role: envs per workgroup (0: the split step is not supported)
+  int split;             // cbev_set_split_step: k_ego_head, then k_raster with the tail
   int obs_h, obs_w;   // wrapped frame size (ResizeObservation); == size when not resizing
   void* area_dev;     // INTER_AREA tables of cbev_set_obs_size
   AreaTab area;
@@ -4130,13 +4393,28 @@ static size_t raster_lds_bytes(const cbev_params& P) {
 }
 static int raster_tiles(int size) { return size == 64 ? Tiles<1>::T : size == 128 ? Tiles<2>::T : Tiles<4>::T; }
 // One step's observation for n records: one workgroup per env.
-static void launch_raster(const cbev_ctx* c, const KArgs& K, void* records, int n, uint8_t* frames, hipStream_t s) {
+// T.ntail leading workgroups run k_ego's tail (the split step); T = {} for the raster alone.
+static void launch_raster(const cbev_ctx* c, const KArgs& K, void* records, int n, uint8_t* frames, hipStream_t s,
+                          const TailArgs& T) {
   const size_t lb = raster_lds_bytes(c->P);
+  const RasterArgs A{K, (uint8_t*)records, n, frames, T};
   switch (c->P.size) {
-    case 64: hipLaunchKernelGGL(k_raster<1>, dim3(n * Tiles<1>::T), dim3(kRasterNT), lb, s, K, (uint8_t*)records, n, frames); break;
-    case 128: hipLaunchKernelGGL(k_raster<2>, dim3(n * Tiles<2>::T), dim3(kRasterNT), lb, s, K, (uint8_t*)records, n, frames); break;
-    default: hipLaunchKernelGGL(k_raster<4>, dim3(n * Tiles<4>::T), dim3(kRasterNT), lb, s, K, (uint8_t*)records, n, frames); break;
+    case 64: hipLaunchKernelGGL(k_raster<1>, dim3(n * Tiles<1>::T), dim3(kRasterNT), lb, s, A); break;
+    case 128: hipLaunchKernelGGL(k_raster<2>, dim3(T.ntail + n * Tiles<2>::T), dim3(kRasterNT), lb, s, A); break;
+    default: hipLaunchKernelGGL(k_raster<4>, dim3(T.ntail + n * Tiles<4>::T), dim3(kRasterNT), lb, s, A); break;
   }
+}
+// Envs per workgroup of k_raster's tail role: the largest group size not above
+// k_ego's (so CBEV_EGO_NE holds) whose record slots, collision scratch and
+// HeroPre fit the raster's LDS, whose size and residency stay what they are.
+// 0: none fits, or S = 64, where k_raster<1> targets 8 waves per SIMD and the
+// tail would spill: those contexts keep the unsplit k_ego.
+static int tail_ne_for(const cbev_params& P, const cbev_caps& C, const cbev_layout& L, int ego_ne) {
+  if (P.size == 64) return 0;
+  const size_t per_env = (size_t)ego_pack(L).bytes + coll_scratch_layout(C, L.vis_words).bytes + sizeof(HeroPre);
+  for (int ne = ego_ne; ne >= 4; ne >>= 1)
+    if (ne * per_env <= raster_lds_bytes(P)) return ne;
+  return 0;
 }
 
 
@@ -4239,6 +4517,8 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
   c->device = device;
   c->ego_ne = ego_ne;
   c->ego_lb = ego_ne * per_env;
+  c->tail_ne = tail_ne_for(P, *caps, lay, ego_ne);
+  c->split = c->tail_ne > 0;  // the default where supported (cbev_set_split_step)
   SgTables T;
   build_sg_tables(&T);
   hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_sg), &T, sizeof T);
@@ -4262,6 +4542,8 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
   c->obs_h = c->obs_w = P.size;
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)k_ego, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute((const void*)k_ego_head, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
   if (e == hipSuccess)
     e = hipFuncSetAttribute(raster_kernel(P.size), hipFuncAttributeMaxDynamicSharedMemorySize, (int)raster_lds_bytes(P));
   if (e == hipSuccess)
@@ -4353,7 +4635,8 @@ int cbev_profile_read(cbev_ctx* c, double* ms3, int64_t* steps) {
   if (steps) *steps = c->prof_n;
   if (!c->prof_ev || c->prof_n == 0) return CBEV_OK;
   HIP_TRY(hipEventSynchronize(c->prof_ev[4 * (c->prof_n - 1) + 3]));
-  // events: 0 before k_actors, 1 after k_actors, 2 after k_ego, 3 after k_raster
+  // events: 0 before k_actors, 1 after k_actors, 2 after k_ego (the split step:
+  // k_ego_head), 3 after k_raster (the split step: with k_ego's tail in it)
   for (int64_t i = 0; i < c->prof_n; ++i) {
     for (int k = 0; k < 3; ++k) {
       float ms = 0.f;
@@ -4376,7 +4659,7 @@ int cbev_profile_raster(cbev_ctx* c, void* records, int n, uint8_t* frames, int 
   HIP_TRY(hipEventCreate(&ev[0]));
   HIP_TRY(hipEventCreate(&ev[1]));
   HIP_TRY(hipEventRecord(ev[0], s));
-  for (int i = 0; i < reps; ++i) launch_raster(c, K, records, n, frames, s);
+  for (int i = 0; i < reps; ++i) launch_raster(c, K, records, n, frames, s, TailArgs{});  // the raster alone
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ev[1], s));
   HIP_TRY(hipEventSynchronize(ev[1]));
@@ -4507,11 +4790,32 @@ int cbev_step(cbev_ctx* c, void* records, int n, const void* actions, uint8_t* f
     K.ep_cap = c->ep_n;
     c->step_count += 1;
   }
-  hipLaunchKernelGGL(k_ego, dim3((n + c->ego_ne - 1) / c->ego_ne), dim3(256), (size_t)c->ego_lb, s,
-                     (uint8_t*)records, n, c->ego_ne, (int)c->L.record_bytes, ego_pack(c->L).n0, ego_pack(c->L).n,
-                     (int)c->L.raw_x, K, actions, reward, ego_term, trunc, cause, info);
+  const EgoPack pk = ego_pack(c->L);
+  TailArgs T{};
+  if (c->split) {
+    // the front, then the raster's launch with the tail as its leading workgroups
+    // (a multiple of 8 of them: the XCD placement of both roles stays)
+    hipLaunchKernelGGL(k_ego_head, dim3((n + c->ego_ne - 1) / c->ego_ne), dim3(256), (size_t)c->ego_lb, s,
+                       (uint8_t*)records, n, c->ego_ne, (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K,
+                       actions);
+    T.ntail = ((n + c->tail_ne - 1) / c->tail_ne + 7) & ~7;
+    T.ne = c->tail_ne;
+    T.rb = (int)c->L.record_bytes;
+    T.n0 = pk.n0;
+    T.np = pk.n;
+    T.raw_x = (int)c->L.raw_x;
+    T.reward = reward;
+    T.term = ego_term;
+    T.trunc = trunc;
+    T.cause = cause;
+    T.info = info;
+  } else {
+    hipLaunchKernelGGL(k_ego, dim3((n + c->ego_ne - 1) / c->ego_ne), dim3(256), (size_t)c->ego_lb, s,
+                       (uint8_t*)records, n, c->ego_ne, (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K,
+                       actions, reward, ego_term, trunc, cause, info);
+  }
   if (ev) HIP_TRY(hipEventRecord(ev[2], s));
-  launch_raster(c, K, records, n, frames, s);
+  launch_raster(c, K, records, n, frames, s, T);
   if (ev) HIP_TRY(hipEventRecord(ev[3], s));
   HIP_TRY(hipGetLastError());
   return CBEV_OK;
@@ -4641,6 +4945,16 @@ int cbev_set_deferred_reset(cbev_ctx* c, int on) {
 }
 
 int cbev_reset_pending(const cbev_ctx* c) { return c && c->pend.on ? 1 : 0; }
+
+int cbev_set_split_step(cbev_ctx* c, int on) {
+  if (!c) return set_err(CBEV_EINVAL, "null argument");
+  if (on && c->tail_ne == 0)
+    return set_err(CBEV_EINVAL, "the split step is not supported at size %d with these capacities: k_ego's tail "
+                                "does not fit k_raster's registers or its %zu bytes of LDS",
+                   c->P.size, raster_lds_bytes(c->P));
+  c->split = on != 0;
+  return CBEV_OK;
+}
 
 int cbev_flush(cbev_ctx* c) {
   if (!c) return set_err(CBEV_EINVAL, "null argument");

@@ -180,6 +180,16 @@ int cbev_reset_pending(const cbev_ctx* ctx);
 /* Launch a recorded deferred reset (k_reset_mask) now; no-op otherwise. */
 int cbev_flush(cbev_ctx* ctx);
 
+/* The split step: cbev_step launches the ego update's front alone (k_ego_head:
+ * everything the observation needs) and its collision / reward / termination
+ * tail as the leading workgroups of the raster's launch, beside the render
+ * instead of before it. Results are bit-identical either way. On by default
+ * where supported; on = 0 selects the unsplit k_ego. Not supported at size 64
+ * or where no tail group fits the raster's LDS: on = 1 then returns
+ * CBEV_EINVAL (cbev_last_error says why) and the unsplit step stays. Host-side
+ * state, taken when cbev_step is called; does not allocate. */
+int cbev_set_split_step(cbev_ctx* ctx, int on);
+
 /* Wrapper stack on the device (wrap_env, envs/__init__.py:62-83). `ring` holds
  * n_frames frames per env (uint8[n_frames][n][h][w], slot `head` the newest;
  * h x w = the cbev_set_obs_size size, the render size by default):
@@ -270,7 +280,9 @@ int cbev_resize_obs(cbev_ctx* ctx, const uint8_t* frames, int n, const uint8_t* 
  * step kernel (used by bench.py for the roofline figure). cbev_profile(ctx, 1)
  * resets the counters and starts recording (up to 8192 steps);
  * cbev_profile_read synchronises on the last event and returns the summed
- * milliseconds of [k_actors, k_ego, k_raster] and the step count. */
+ * milliseconds of [k_actors, k_ego, k_raster] and the step count (the split
+ * step: the second span is k_ego_head, the third k_raster's launch with the ego
+ * tail in it; cbev_profile_raster below always times the raster alone). */
 int cbev_profile(cbev_ctx* ctx, int enable);
 int cbev_profile_read(cbev_ctx* ctx, double* ms3, int64_t* steps);
 
