@@ -829,6 +829,19 @@ __device__ __forceinline__ void ego_stage_out(Slot slot, uint8_t* __restrict__ r
   }
 }
 
+// the same for the envs whose bit of `frozen` is clear (k_ego_rep: no bank slots)
+__device__ __forceinline__ void ego_stage_out_live(const uint8_t* lds, uint8_t* __restrict__ recs, int e0, int ne,
+                                                   const KArgs& K, const EgoPack& p, uint64_t frozen) {
+  const int nhh = (int)(K.L.cx / 16), nout = nhh + p.nvis;
+  const int64_t rb = K.L.record_bytes;
+  for (int q = threadIdx.x; q < ne * nout; q += 256) {
+    const int k = q / nout, j = q - k * nout;
+    if ((frozen >> k) & 1ull) continue;
+    const int c = j < nhh ? j : p.vis_c + (j - nhh);
+    *(uint4*)(recs + (int64_t)(e0 + k) * rb + ego_src(p.n0, p.raw_x, c)) = *(const uint4*)(lds + k * p.bytes + 16 * c);
+  }
+}
+
 // Does the whole output sample inside the crop with the rotated surface covering
 // it? Then raster_out runs without per-pixel tests and only the crop texels
 // the output can sample need staging. The map from output pixels to source
@@ -1510,6 +1523,25 @@ __global__ __launch_bounds__(256) void k_actors(KArgs K, uint8_t* __restrict__ r
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_actors_g4(KArgs K,
                                                                                           uint8_t* __restrict__ recs,
                                                                                           int n) {
+  actors_body<false, 4>(K, recs, n);
+}
+// Substeps 2.. of cbev_step_repeat: the same bodies behind a gate. A wave whose
+// env has terminated within this agent step (its term byte, written by the
+// previous substep's ego kernel) is frozen: it exits before it loads anything
+// else. One env per wave, so the test is wave-uniform.
+__device__ __forceinline__ bool actors_frozen(const uint8_t* __restrict__ term, int n) {
+  const int e = xcd_env4_of_wg(blockIdx.x, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n);
+  return e < n && term[e] != 0;
+}
+template <bool WIDE, int MINAW>
+__global__ __launch_bounds__(256) void k_actors_rep(KArgs K, uint8_t* __restrict__ recs, int n,
+                                                    const uint8_t* __restrict__ term) {
+  if (actors_frozen(term, n)) return;
+  actors_body<WIDE, MINAW>(K, recs, n);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_actors_g4_rep(
+    KArgs K, uint8_t* __restrict__ recs, int n, const uint8_t* __restrict__ term) {
+  if (actors_frozen(term, n)) return;
   actors_body<false, 4>(K, recs, n);
 }
 
@@ -3270,7 +3302,13 @@ __device__ __forceinline__ void ego_tail_out(const uint8_t* lds, uint8_t* __rest
 // S5-S7 for the workgroup's envs. WHOLE (k_ego): after ego_front in the same
 // workgroup, on its LDS and C. Otherwise k_raster's tail role: the records are
 // the head's (a folded reset already applied: no bank slots), staged in here.
-template <bool WHOLE>
+// GATED (k_ego_rep, substeps 2.. of cbev_step_repeat): an env whose term byte of
+// this agent step is set is frozen. Its S6 does not run (no collide_env, so no
+// episode row, no termination count, no tcount), its outputs stay as the
+// terminal substep left them and none of its record is written back; what the
+// front and S5 computed for it stays in LDS. A live env's reward is added to
+// the agent step's sum, its other outputs are overwritten.
+template <bool WHOLE, bool GATED = false>
 __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ recs, int n, int ne, int st_rb,
                                          int st_n0, int st_n, int st_raw_x, const KArgs& K,
                                          double* __restrict__ reward_out, uint8_t* __restrict__ term_out,
@@ -3327,6 +3365,8 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
     __syncthreads();  // the staging has landed; the prologue's scratch in LDS
   }
   const uint32_t tc0 = C.tc0;
+  uint64_t frozen = 0ull;  // bit k: env e0 + k (each wave builds the workgroup's mask: ne <= 64)
+  if (GATED) frozen = __ballot(lane < ne_eff && term_out[e0 + (lane < ne_eff ? lane : 0)] != 0);
   CBEV_STAMP(1, 0);
   // S5 (env k, element i) pairs: env k = tid / tpe, elements sub, sub + tpe, ...
   {
@@ -3467,12 +3507,15 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
   __syncthreads();
   CBEV_STAMP(1, 1);
   // S6
-  if (tid < ne_eff) {
+  if (tid < ne_eff && !(GATED && ((frozen >> tid) & 1ull))) {
     const DRec r = rec(tid);
     CollPre cp = coll_reduce_serial(scr + tid * SL.bytes, SL, r.hi[CBEV_HI_NACT], r.hi[CBEV_HI_NRAW]);
     cp.spx = C.spx;  // tid < ne: wave 0, the lane that loaded them in S4
     cp.spy = C.spy;
+    double rsum = 0.0;
+    if (GATED) rsum = reward_out[e0 + tid];  // r1 + .. + r(j-1)
     collide_env(K, r, e0 + tid, cp, reward_out, term_out, trunc_out, cause_out, info_out);
+    if (GATED) reward_out[e0 + tid] = rsum + r.hd[CBEV_HD_REWARD];
     if (r.hi[CBEV_HI_TERM]) K.tcount[e0 + tid] = tc0 + 1u;  // the next reset's bank row moves on
   }
   __syncthreads();
@@ -3481,6 +3524,10 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
   if (!WHOLE) {
     ego_tail_out(lds, recs, e0, ne_eff, K, pk);
     CBEV_STAMP(1, 3);
+    return;
+  }
+  if (GATED) {  // no folded reset here (cbev_step_repeat flushes it): HD, HI and the vis group of the live envs
+    ego_stage_out_live(lds, recs, e0, ne_eff, K, pk, frozen);
     return;
   }
   ego_stage_out(slot, recs, e0, ne_eff, K, pk);
@@ -3506,6 +3553,22 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
   if (!ego_front<true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C)) return;
   ego_tail<true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out, trunc_out, cause_out,
                  info_out, C);
+}
+
+// Substeps 2.. of cbev_step_repeat: k_ego with the gated, accumulating tail.
+// The front runs for every env (it changes LDS only; an action index out of
+// range was flagged by substep 1, which nothing freezes). K.rmask is null: the
+// call flushes a deferred reset before substep 1.
+__global__ __launch_bounds__(256) void k_ego_rep(uint8_t* __restrict__ recs, int n, int ne, int st_rb, int st_n0,
+                                                 int st_n, int st_raw_x, KArgs K, const void* __restrict__ actions,
+                                                 double* __restrict__ reward_out, uint8_t* __restrict__ term_out,
+                                                 uint8_t* __restrict__ trunc_out, int32_t* __restrict__ cause_out,
+                                                 float* __restrict__ info_out) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  EgoCarry C;
+  if (!ego_front<true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C)) return;
+  ego_tail<true, true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out, trunc_out, cause_out,
+                       info_out, C);
 }
 
 // The split step's first launch: the front alone. It reads the previous step's
@@ -4378,6 +4441,10 @@ static ActorsKernel actors_kernel(const cbev_caps& C) {
   // config 4; 2 lanes per actor at 4 waves per SIMD spills: 30.7 us)
   return C.actor_cap > 64 ? k_actors<true, 1> : C.actor_cap > 32 ? k_actors<false, 1> : k_actors_g4;
 }
+typedef void (*ActorsRepKernel)(KArgs, uint8_t*, int, const uint8_t*);
+static ActorsRepKernel actors_rep_kernel(const cbev_caps& C) {  // actors_kernel's choice, gated
+  return C.actor_cap > 64 ? k_actors_rep<true, 1> : C.actor_cap > 32 ? k_actors_rep<false, 1> : k_actors_g4_rep;
+}
 static const void* raster_kernel(int size) {
   return size == 64 ? (const void*)k_raster<1> : size == 128 ? (const void*)k_raster<2> : (const void*)k_raster<4>;
 }
@@ -4544,6 +4611,8 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
     e = hipFuncSetAttribute((const void*)k_ego, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)k_ego_head, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute((const void*)k_ego_rep, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
   if (e == hipSuccess)
     e = hipFuncSetAttribute(raster_kernel(P.size), hipFuncAttributeMaxDynamicSharedMemorySize, (int)raster_lds_bytes(P));
   if (e == hipSuccess)
@@ -4816,6 +4885,65 @@ int cbev_step(cbev_ctx* c, void* records, int n, const void* actions, uint8_t* f
   }
   if (ev) HIP_TRY(hipEventRecord(ev[2], s));
   launch_raster(c, K, records, n, frames, s, T);
+  if (ev) HIP_TRY(hipEventRecord(ev[3], s));
+  HIP_TRY(hipGetLastError());
+  return CBEV_OK;
+}
+
+// Action repeat: `repeat` simulation substeps with the same actions, one render.
+// Substep 1 is cbev_step's k_actors + unsplit k_ego; substeps 2.. are the gated
+// kernels (an env that terminated within this agent step is frozen from its
+// terminal substep on); then the raster alone, from the records as they stand.
+// One linear chain on `stream`, nothing allocated.
+int cbev_step_repeat(cbev_ctx* c, void* records, int n, const void* actions, int repeat, uint8_t* frames,
+                     double* reward, uint8_t* term, uint8_t* trunc, int32_t* cause, float* info, void* stream) {
+  if (!c || !records || !actions || !frames || !reward || !term || !trunc || !cause)
+    return set_err(CBEV_EINVAL, "null argument");
+  if (repeat < 1 || repeat > CBEV_REPEAT_MAX)
+    return set_err(CBEV_EINVAL, "repeat %d outside [1, %d]", repeat, CBEV_REPEAT_MAX);
+  if (repeat == 1) return cbev_step(c, records, n, actions, frames, reward, term, trunc, cause, info, stream);
+  if (!c->map_dev) return set_err(CBEV_ESTATE, "cbev_set_map not called");
+  if (n <= 0) return CBEV_OK;
+  if (c->stats && n > c->ep_n) return set_err(CBEV_EINVAL, "n %d exceeds the %d envs of the episode stats", n, c->ep_n);
+  // a deferred reset is launched now: k_ego marks a folded reset's bank row in
+  // RS_FAST, which the next substep's render set-up would overwrite before the
+  // one raster at the end could copy the bank frame into the ring
+  CBEV_FLUSH(c);
+  hipStream_t s = (hipStream_t)stream;
+  KArgs K = kargs(c);
+  c->last_term = term;
+  c->last_n = n;
+  if (n > c->seq_n) c->seq_n = n;
+  if (c->stats) {  // every substep's rows into this agent step's slot
+    const int slot = (int)(c->step_count % c->ep_ring), next = (slot + 1) % c->ep_ring;
+    K.ep_rows = c->ep_rows + (int64_t)slot * c->ep_n * CBEV_EP_COUNT;
+    K.ep_count = c->ep_counts + slot;
+    K.ep_count_next = c->ep_counts + next;
+    K.ep_cap = c->ep_n;
+    c->step_count += 1;
+  }
+  const int wg4 = (n + 3) / 4;
+  const dim3 ego_grid((n + c->ego_ne - 1) / c->ego_ne);
+  const EgoPack pk = ego_pack(c->L);
+  // events: 0 before substep 1, 1 after its k_actors, 2 after the last substep's
+  // ego kernel, 3 after k_raster
+  hipEvent_t* ev = nullptr;
+  if (c->prof_on && c->prof_n < CBEV_PROF_MAX) ev = c->prof_ev + 4 * c->prof_n++;
+  if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+  if (c->C.actor_cap > 0) hipLaunchKernelGGL(actors_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n);
+  if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+  hipLaunchKernelGGL(k_ego, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n, c->ego_ne,
+                     (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, reward, term, trunc, cause, info);
+  for (int j = 2; j <= repeat; ++j) {
+    if (c->C.actor_cap > 0)
+      hipLaunchKernelGGL(actors_rep_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n,
+                         (const uint8_t*)term);
+    hipLaunchKernelGGL(k_ego_rep, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n, c->ego_ne,
+                       (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, reward, term, trunc, cause,
+                       info);
+  }
+  if (ev) HIP_TRY(hipEventRecord(ev[2], s));
+  launch_raster(c, K, records, n, frames, s, TailArgs{});  // the raster alone
   if (ev) HIP_TRY(hipEventRecord(ev[3], s));
   HIP_TRY(hipGetLastError());
   return CBEV_OK;

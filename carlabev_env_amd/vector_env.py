@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import layout as LY
-from ._lib import OBS_F16, OBS_F32, OBS_U8, check, lib
+from ._lib import OBS_F16, OBS_F32, OBS_U8, REPEAT_MAX, check, lib
 from .config import EnvConfig, RunConfig, validate_run_config, get_action_profile_spec
 from .params import CbevParams, build_params, load_class_map, padded_map
 from .host_reset import HostResetBuilder
@@ -120,7 +120,7 @@ class CarlaBEVVectorEnv:
 
     def __init__(self, cfg, *, num_envs: int | None = None, device=None, caps: dict | None = None,
                  info_mode: str = "full", scene_generator=None, wrappers: bool = True, copy_obs: bool = True,
-                 defer_reset: bool = True, reset_pool=None, obs_dtype: str = "float32"):
+                 defer_reset: bool = True, reset_pool=None, obs_dtype: str = "float32", action_repeat: int = 1):
         """wrappers=False gives the base `CarlaBEV` observation of every env, as a
         `SyncVectorEnv` of unwrapped `CarlaBEV(cfg)` would: (S, S, 3) uint8 RGB for the
         BEV modes, float32[7] for obs_mode="vector" (carlabev.py:233-244, spaces.py:54-61).
@@ -162,7 +162,19 @@ class CarlaBEVVectorEnv:
         pixel p in bit p & 7 of byte p >> 3; unpack_obs() expands it) carry the same
         observation in 1/2, 1/4 and 1/32 of the bytes. "uint8" and "bits" refuse
         vehicle_weighted; every other observation mode (gray, wrappers=False)
-        is uint8 or 7 floats already and refuses anything but "float32"."""
+        is uint8 or 7 floats already and refuses anything but "float32".
+
+        action_repeat: simulation substeps per step() with the same action and one
+        observation (cbev_step_repeat), as a FrameSkip(k) wrapper directly around each
+        env, inside the frame stack: an int in [1, 64], 1 (default) = the reference's
+        step. The reward is the sum over the substeps an env ran; an env that
+        terminates in a substep is frozen for the rest of the step, and its
+        observation is the frame of its terminal substep. max_actions, the episode
+        length and the episode statistics count substeps."""
+        if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or not (
+                1 <= int(action_repeat) <= REPEAT_MAX):
+            raise ValueError(f"action_repeat={action_repeat!r}: an int in [1, {REPEAT_MAX}]")
+        self.action_repeat = int(action_repeat)
         if isinstance(cfg, RunConfig):
             raw = cfg
         elif isinstance(cfg, dict) and "env" in cfg:
@@ -718,8 +730,12 @@ class CarlaBEVVectorEnv:
         frames = self._p_full if self.resize else self._p_ring + self.head * self._slot_bytes
         rec, rew, term, trunc, cause, info = self._p_step
         stream = self._stream()
-        check(lib().cbev_step(self._ctx, rec, self.num_envs, a.data_ptr(), frames, rew, term, trunc, cause, info,
-                              stream), "cbev_step")
+        if self.action_repeat == 1:
+            check(lib().cbev_step(self._ctx, rec, self.num_envs, a.data_ptr(), frames, rew, term, trunc, cause, info,
+                                  stream), "cbev_step")
+        else:
+            check(lib().cbev_step_repeat(self._ctx, rec, self.num_envs, a.data_ptr(), self.action_repeat, frames, rew,
+                                         term, trunc, cause, info, stream), "cbev_step_repeat")
         self._reset_pending = False  # taken by this step (or launched before it)
         self._step_stream = stream.value or 0  # the step's rows are waited for on this stream (StepInfos)
         self._stepped = True

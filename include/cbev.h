@@ -64,6 +64,28 @@ int cbev_set_map(cbev_ctx* ctx, const uint8_t* padded_map_host, int64_t bytes);
 int cbev_step(cbev_ctx* ctx, void* records, int n, const void* actions, uint8_t* frames, double* reward,
               uint8_t* term, uint8_t* trunc, int32_t* cause, float* info, void* stream);
 
+/* Action repeat (frame skip): `repeat` CarlaBEV.step calls with the same
+ * actions and one observation, as a FrameSkip(repeat) wrapper directly around
+ * each env would give. Substep 1 is cbev_step's (nothing freezes it). An env
+ * whose substep j < repeat was terminal (term, truncation included) is frozen
+ * for the rest of the call: its record is not touched, its actors do not move,
+ * it writes no second episode row and counts no second termination.
+ *   reward       r1 + .. + rj in float64, in that order (j: the env's last executed substep)
+ *   term, trunc, cause, info   those of the env's last executed substep
+ *   frames       one render at the end, of every record as it then stands
+ * KSTEPS (max_actions), EP_LEN and the episode accumulators count substeps.
+ * With episode statistics every substep's rows go into the same ring slot (the
+ * slot advances once per call; an env terminates at most once per call).
+ * repeat == 1 is cbev_step. repeat outside [1, CBEV_REPEAT_MAX] is CBEV_EINVAL
+ * before anything is launched. A deferred reset is launched (as by cbev_flush)
+ * rather than folded. All launches are one chain on `stream`; nothing is
+ * allocated. cbev_reset_terminated after it resets the envs whose term is set.
+ * With cbev_profile on, a call with repeat > 1 records: before substep 1,
+ * after its k_actors, after the last substep's ego kernel, after k_raster. */
+#define CBEV_REPEAT_MAX 64
+int cbev_step_repeat(cbev_ctx* ctx, void* records, int n, const void* actions, int repeat, uint8_t* frames,
+                     double* reward, uint8_t* term, uint8_t* trunc, int32_t* cause, float* info, void* stream);
+
 /* Episode statistics on the device (Stats, src/deeprl/stats.py:87-148, and
  * CarlaBEV._check_termination, carlabev.py:177-185), so `infos["episode_info"]`
  * needs no per-step host work. The caller owns the buffers (device memory):
