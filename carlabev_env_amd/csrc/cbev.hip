@@ -4556,6 +4556,9 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
   if (P.crop < P.size || P.crop > 400) return set_err(CBEV_EINVAL, "crop %d out of range", P.crop);
   if (P.map_pitch % 16 != 0 || P.map_pitch < P.render_w) return set_err(CBEV_EINVAL, "bad map pitch %d", P.map_pitch);
   if (P.render_w != P.map_w + 2 * P.pad || P.render_h != P.map_h + 2 * P.pad) return set_err(CBEV_EINVAL, "bad render shape");
+  // d_crop_origin clamps the origin into [0, render - crop]: the staging reads a crop-wide window from there
+  if (P.render_w < P.crop || P.render_h < P.crop)
+    return set_err(CBEV_EINVAL, "render surface %d x %d smaller than crop %d", P.render_w, P.render_h, P.crop);
   if (P.action_kind == 0 && (P.n_discrete < 1 || P.n_discrete > 16)) return set_err(CBEV_EINVAL, "bad n_discrete");
   if (caps->route_cap < 2 || caps->actor_cap < 0 || caps->actor_route_cap < 0 || caps->tl_cap < 0)
     return set_err(CBEV_EINVAL, "bad capacities");

@@ -8,6 +8,8 @@ that mostly fails there.
   raster_batch     one env per (heading, position): V = 0 and action 0, so the
                    pose stays where it was put; the scene is painted relative to
                    the env's own crop origin
+  reduced_world    the same matrix under a crop smaller than the reference's
+                   (REDUCED_GEOMETRIES): the raster's checked output path
   many_actor_batch more than 64 actors in one crop (paint loops past thread 63)
   long_route_batch ego routes of 33-128 points, single-step placements on chosen
                    targets and "drive" envs that cross vis word boundaries
@@ -34,6 +36,26 @@ import raster_ref
 # 0.8 gives crop 482, which cbev_create refuses (crop above 400).
 GEOMETRIES = ((64, 0.5), (64, 0.2), (128, 0.5), (128, 0.2), (256, 0.5), (256, 0.6))
 
+# (size, ego_anchor_y_frac, crop, pad): crops below ceil(2 hypot(mx, my)), which
+# cbev_create accepts (any crop in [size, 400]) and the vector env never builds.
+# The rotated surface no longer covers the output and samples leave the crop:
+# the checked output path (tile_out_check, crop_background, windows clipped by
+# the crop). The centred anchors take pad = crop (the render surface rebuilt);
+# those at 0.2 keep build_params's pad, so pad != crop, and their surface misses
+# part of the output (black). The last one puts the anchor on the output's top
+# row: near the axes the lower two of its four tiles lie wholly past the crop
+# (a one-row window). With the anchor column centred the surface always spans
+# the output's columns, so two more take a fifth entry, the anchor's x fraction:
+# the surface ends inside the output on the right and below (0.2, 0.2), on the
+# left and above (0.8, 0.8).
+REDUCED_GEOMETRIES = ((64, 0.5, 64, 64), (64, 0.2, 70, 119), (128, 0.5, 128, 128), (128, 0.2, 150, 241),
+                      (256, 0.5, 256, 256), (256, 0.2, 400, 482), (256, 0.0, 256, 256),
+                      (128, 0.2, 150, 241, 0.2), (128, 0.8, 150, 241, 0.8))
+
+
+def reduced_id(geo):
+    return "-".join(str(g) for g in geo[:2]) + f"-crop{geo[2]}-pad{geo[3]}" + (f"-ax{geo[4]}" if len(geo) > 4 else "")
+
 CAPS_RASTER = LY.Caps(128, 8, 16, 4)      # small records: a raster batch has hundreds of envs
 CAPS_MANY = LY.Caps(128, 96, 288, 4)      # more than 64 actor slots
 CAPS_EGO8 = LY.Caps(128, 32, 288, 4)      # k_ego stages 8 envs per workgroup
@@ -51,6 +73,25 @@ def authored_world(size, anchor_y=0.5, reward_profile="carl_base_v1"):
     P = build_params(cfg, classes)
     padded, pitch = padded_map(classes, P.pad)
     assert pitch == P.map_pitch
+    return P, padded, classes
+
+
+@lru_cache(maxsize=None)
+def reduced_world(size, anchor_y, crop, pad, anchor_x=None):
+    """(P, padded map, class map) of authored_world(size, anchor_y) with a smaller
+    crop: pad either stays build_params's (pad != crop, the map as it was) or
+    becomes the crop, with the render surface and the padded map rebuilt.
+    anchor_x: a fraction that moves the anchor column off the centre as well."""
+    P0, padded, classes = authored_world(size, anchor_y)
+    P = type(P0).from_buffer_copy(P0)
+    assert size <= crop < P0.crop and pad in (crop, P0.pad)
+    P.crop = crop
+    if anchor_x is not None:
+        P.anchor_x = int(round((size - 1) * anchor_x))
+    if pad != P0.pad:
+        P.pad = pad
+        P.render_w, P.render_h = P.map_w + 2 * pad, P.map_h + 2 * pad
+        padded, P.map_pitch = padded_map(classes, pad)
     return P, padded, classes
 
 
@@ -89,13 +130,18 @@ def raster_headings(step_deg=1.5):
     return out
 
 
-def raster_positions(P):
+def raster_positions(P, mirrored=False):
     """World positions (x, y): mid-map and its offsets (xmin & 3 takes all four
-    values), the map's corners, and one point more than crop / 2 outside the map
-    on both axes (the crop origin clamps at 0 in x and at its maximum in y)."""
+    values), the map's corners, and one point 5 texels past where the crop
+    origin starts to clamp on both axes (at 0 in x and at its maximum in y; with
+    pad = crop that is more than crop / 2 outside the map). mirrored: also the
+    opposite point (the maximum in x, 0 in y), so both clamps of both axes, and
+    the last rows and columns of the byte maps, are staged."""
     mx, my = P.map_w // 2 + 0.0, P.map_h // 2 + 0.0
-    return [(mx, my), (mx + 1, my + 2), (mx + 2, my + 3), (mx + 3.5, my + 0.5), (3.0, 3.0),
-            (P.map_w - 2.0, P.map_h - 2.0), (-(P.crop / 2.0) - 5.0, P.map_h + P.crop / 2.0 + 5.0)]
+    lo, hi = P.crop / 2.0 - P.pad - 5.0, P.pad - P.crop / 2.0 + 5.0
+    pos = [(mx, my), (mx + 1, my + 2), (mx + 2, my + 3), (mx + 3.5, my + 0.5), (3.0, 3.0),
+           (P.map_w - 2.0, P.map_h - 2.0), (lo, P.map_h + hi)]
+    return pos + [(P.map_w + hi, lo)] if mirrored else pos
 
 
 def _serpentine(n, C):
@@ -157,9 +203,9 @@ def clear_every_fifth_target(view):
         view.vis[i >> 5] &= np.uint32(~(1 << (i & 31)) & 0xFFFFFFFF)
 
 
-def raster_cases(P, step_deg=1.5):
+def raster_cases(P, step_deg=1.5, mirrored=False):
     """(angle, x, y) per env: all headings at the first position, every fifth at the others."""
-    heads, pos = raster_headings(step_deg), raster_positions(P)
+    heads, pos = raster_headings(step_deg), raster_positions(P, mirrored)
     cases = [(a, *pos[0]) for a in heads]
     for p in pos[1:]:
         cases += [(a, *p) for a in heads[::5]]
@@ -176,12 +222,20 @@ def raster_step_deg(size):
     return 3.0 if size >= 256 else 1.5
 
 
-def raster_batch(size, anchor_y, step_deg=None):
+def reduced_step_deg(size):
+    """The reduced-crop geometries' heading grid: 6 degrees, 12 at size 256."""
+    return 12.0 if size >= 256 else 6.0
+
+
+def raster_batch(size, anchor_y, step_deg=None, world=None):
     """(P, padded, caps, recs, layout, acts): the raster matrix of one geometry.
-    acts: action 0 (nothing pressed), then gas."""
-    P, padded, _ = authored_world(size, anchor_y)
-    step_deg = raster_step_deg(size) if step_deg is None else step_deg
-    cases = raster_cases(P, step_deg)
+    acts: action 0 (nothing pressed), then gas. world: the (P, padded map) of a
+    reduced-crop geometry (reduced_world) instead of authored_world's; its matrix
+    takes the coarser grid and the mirrored clamp position as well."""
+    P, padded = authored_world(size, anchor_y)[:2] if world is None else world
+    if step_deg is None:
+        step_deg = raster_step_deg(size) if world is None else reduced_step_deg(size)
+    cases = raster_cases(P, step_deg, mirrored=world is not None)
     specs = []
     for k, (a, x, y) in enumerate(cases):
         xm, ym = raster_ref.crop_origin(P, x, y)
@@ -289,6 +343,8 @@ def raster_classes(P, x, y, yaw, NT=256):
                 xs.append(dx >> 16)
                 ys.append(dy >> 16)
             clipped = min(xs) < 0 or min(ys) < 0 or max(xs) > C - 1 or max(ys) > C - 1
+            # the whole tile lies past one side of the crop: tile_window clamps it to one row or column of texels
+            no_texel = max(xs) < 0 or max(ys) < 0 or min(xs) > C - 1 or min(ys) > C - 1
             xl, yl = min(max(min(xs), 0), C - 1), min(max(min(ys), 0), C - 1)
             xh, yh = max(min(max(xs), C - 1), xl), max(min(max(ys), C - 1), yl)
             tr = abs(isin) > abs(icos)
@@ -299,11 +355,13 @@ def raster_classes(P, x, y, yaw, NT=256):
             c0 = (ushift + ul) >> 4
             nc = ((ushift + uh) >> 4) - c0 + 1
             dr = NT // nc
-            off_surface = (ox0 - rx0 < 0 or ox0 + TC - 1 - rx0 >= nx or oy0 - ry0 < 0 or oy0 + TR - 1 - ry0 >= ny)
+            off = dict(off_left=ox0 - rx0 < 0, off_right=ox0 + TC - 1 - rx0 >= nx, off_top=oy0 - ry0 < 0,
+                       off_bottom=oy0 + TR - 1 - ry0 >= ny)  # the side of the rotated surface the tile passes
+            off_surface = any(off.values())
             out.append(dict(r90=r90, near_axis=(not r90) and (isin == 0 or icos == 0), transposed=tr, fast=fast,
                             ushift=ushift, nc=nc, nv=nv, leftover=NT % nc != 0, passes_gt4=(nv + dr - 1) // dr > 4,
-                            clipped=clipped, outside=outside, off_surface=off_surface, clamped=clamped,
-                            lds=nv * (16 * nc + 4)))
+                            clipped=clipped, outside=outside, no_texel=no_texel, off_surface=off_surface, clamped=clamped,
+                            lds=nv * (16 * nc + 4), **off))
     return out
 
 
@@ -318,12 +376,15 @@ def class_labels(tile):
             "passes_gt4" if t["passes_gt4"] else "passes_le4",
             "clipped" if t["clipped"] else "unclipped",
             "outside" if t["outside"] else "inside",
-            "clamped" if t["clamped"] else "unclamped"]
+            "no_texel" if t["no_texel"] else "some_texel",
+            "off_surface" if t["off_surface"] else "on_surface",
+            "clamped" if t["clamped"] else "unclamped"] + [k for k in OFF_SIDES if t[k]]
 
 
+OFF_SIDES = ("off_left", "off_right", "off_top", "off_bottom")
 ALL_CLASSES = ("r90", "near_axis", "general", "transposed", "upright", "fast", "check", "ushift0", "ushift1", "ushift2",
                "ushift3", "nc_leftover", "nc_divides", "passes_gt4", "passes_le4", "clipped", "unclipped", "outside",
-               "inside", "clamped", "unclamped")
+               "inside", "no_texel", "some_texel", "off_surface", "on_surface", "clamped", "unclamped") + OFF_SIDES
 
 
 # ------------------------------------------------------------------ long ego routes

@@ -16,6 +16,7 @@ from carlabev_env_amd import layout as LY
 from carlabev_env_amd import routes
 
 GEO_IDS = [f"{s}-{a}" for s, a in EC.GEOMETRIES]
+REDUCED_IDS = [EC.reduced_id(g) for g in EC.REDUCED_GEOMETRIES]
 
 # Classes of raster_classes a geometry cannot reach, by name, with the reason.
 # A 0.01 degree heading scan at a mid-map, an offset and a clamped position
@@ -30,7 +31,8 @@ _LARGE = "128 x 128 tiles: at least 128 window rows over at most 28 rows per pas
 _NC128 = "128 x 128 tiles: 9 to 13 chunks per window row, none of which divides 256"
 _NC64 = ("64 x 64 tiles: 5 to 7 chunks per row, and 4 only for a 64-texel row that starts on a 16-byte boundary, which "
          "no heading of the scan does with this crop's anchor and origin parity")
-_ALWAYS = {"check": _ENCLOSED, "clipped": _ENCLOSED, "outside": _ENCLOSED}
+_ALWAYS = dict({"check": _ENCLOSED, "clipped": _ENCLOSED, "outside": _ENCLOSED, "no_texel": _ENCLOSED,
+                "off_surface": _ENCLOSED}, **{k: _ENCLOSED for k in EC.OFF_SIDES})
 EXCLUDED = {
     (64, 0.5): dict(_ALWAYS, ushift2=_PARITY, passes_gt4=_SMALL),
     (64, 0.2): dict(_ALWAYS, ushift2=_PARITY, passes_gt4=_SMALL, nc_divides=_NC64),
@@ -39,6 +41,51 @@ EXCLUDED = {
     (256, 0.5): dict(_ALWAYS, ushift2=_PARITY, passes_le4=_LARGE, nc_divides=_NC128),
     (256, 0.6): dict(_ALWAYS, ushift2=_PARITY, passes_le4=_LARGE, nc_divides=_NC128),
 }
+# The reduced-crop geometries (EC.REDUCED_GEOMETRIES, keys (size, anchor_y, crop, pad)).
+_COVERED = ("crop = size around a centred anchor (size / 2): the rotated surface is at least size wide and high at "
+            "every heading and centred on the anchor, so it covers the output; only samples leave the crop")
+_NEVER_IN = ("the output corners opposite the anchor are 59 (size 64) and at least 120 (size 128) texels from it, farther than "
+             "the crop's own corners (70 / sqrt 2 = 49, 150 / sqrt 2 = 106): they sample outside the crop at every "
+             "heading, and the one tile an env has at these sizes is clipped with them")
+_NEVER_FAST400 = ("the two output corners opposite the anchor are 241 texels from it and 64 degrees apart; a 400-texel "
+                  "crop holds such a point only within 11 degrees of its diagonals, which are 90 degrees apart, so one "
+                  "of the two always samples outside")
+_BELOW = ("anchor row 13 of 64: the rotated surface of a 70-texel crop is at most 98 rows high and centred there, so "
+          "it ends at row 62 or above, and the one tile of every env has rows past it")
+_NC5 = "a 64 x 64 tile under a 70-texel crop: windows of 64 to 70 texels from any offset take 5 chunks, never 4"
+_NC9 = ("a 128 x 128 tile under a 150-texel crop with the anchor column centred: windows of 9 or 10 chunks per row, "
+        "neither divides 256")
+_NC400 = "128 x 128 tiles under a 400-texel crop: 9 to 13 chunks per window row, none of which divides 256"
+_SMALL64 = "64 x 64 tiles: at most 70 window rows over at least 51 rows per pass, never more than 2 passes"
+_LARGE400 = ("128 x 128 tiles under a 400-texel crop: the crop clips a corner of the lower tiles only, at least 123 "
+             "window rows stay, over at most 28 rows per pass: never fewer than 5 passes")
+_NEAR = ("every tile has a pixel within crop / 2 of the anchor (77 texels at most, the lower tiles of (256, 0.2)), which "
+         "samples inside the crop at every heading")
+_TOP_ROW = ("the anchor is on the output's top row: the rotated surface of a 256-texel crop, centred there, ends at "
+            "row 181 or above, so it never covers the output")
+_SIDE = ("the rotated surface is at least crop wide and high and centred on the anchor: it ends inside the output only "
+         "on a side that is more than crop / 2 from the anchor, which this side is not")
+
+
+def _only(*sides):
+    """The sides of the rotated surface that never end inside the output: all but `sides`."""
+    return {k: _SIDE for k in EC.OFF_SIDES if k not in sides}
+
+
+_OFF_CENTRE_128 = dict(no_texel=_NEAR, fast=_NEVER_IN, unclipped=_NEVER_IN, inside=_NEVER_IN)
+EXCLUDED.update({
+    (64, 0.5, 64, 64): dict(_only(), no_texel=_NEAR, off_surface=_COVERED, passes_gt4=_SMALL64),
+    (64, 0.2, 70, 119): dict(_only("off_bottom"), no_texel=_NEAR, fast=_NEVER_IN, unclipped=_NEVER_IN, inside=_NEVER_IN,
+                             on_surface=_BELOW, nc_divides=_NC5, passes_gt4=_SMALL64),
+    (128, 0.5, 128, 128): dict(_only(), no_texel=_NEAR, off_surface=_COVERED),
+    (128, 0.2, 150, 241): dict(_only("off_bottom"), nc_divides=_NC9, **_OFF_CENTRE_128),
+    (256, 0.5, 256, 256): dict(_only(), no_texel=_NEAR, off_surface=_COVERED),
+    (256, 0.2, 400, 482): dict(_only("off_bottom"), no_texel=_NEAR, fast=_NEVER_FAST400, nc_divides=_NC400,
+                               passes_le4=_LARGE400),
+    (256, 0.0, 256, 256): dict(_only("off_bottom"), fast=_TOP_ROW),
+    (128, 0.2, 150, 241, 0.2): dict(_only("off_bottom", "off_right"), **_OFF_CENTRE_128),
+    (128, 0.8, 150, 241, 0.8): dict(_only("off_top", "off_left"), **_OFF_CENTRE_128),
+})
 
 
 def _step_and_restate(P, padded, layout, orc, rec, action, frame):
@@ -79,12 +126,24 @@ def _painted_corner(P, padded, view):
 
 @pytest.mark.parametrize("geo", EC.GEOMETRIES, ids=GEO_IDS)
 def test_raster_matrix_oracle_equals_numpy_and_covers_every_class(geo):
-    size, ay = geo
-    P, padded, caps, recs, layout, acts = EC.raster_batch(size, ay)
+    _matrix_oracle_equals_numpy_and_covers_every_class(geo, EC.raster_batch(*geo))
+
+
+@pytest.mark.parametrize("geo", EC.REDUCED_GEOMETRIES, ids=REDUCED_IDS)
+def test_reduced_crop_matrix_oracle_equals_numpy_and_covers_every_class(geo):
+    """The same matrix over a crop smaller than the reference's: the checked
+    output path. These frames are what test_raster_matrix_reduced_crop
+    (test_gpu_edge_cases.py) compares the device with."""
+    _matrix_oracle_equals_numpy_and_covers_every_class(geo, EC.raster_batch(*geo[:2], world=EC.reduced_world(*geo)[:2]))
+
+
+def _matrix_oracle_equals_numpy_and_covers_every_class(geo, batch):
+    size, ay = geo[:2]
+    P, padded, caps, recs, layout, acts = batch
     orc = O.Oracle(P, padded, caps.c(), layout.record_bytes)
     S = P.size
     frame = np.zeros((S, S), np.uint8)
-    hist, colours, bg_differs = collections.Counter(), collections.Counter(), 0
+    hist, colours, bg_differs, black_envs = collections.Counter(), collections.Counter(), 0, 0
     for e in range(len(recs)):
         v = LY.RecordView(recs[e], layout)
         orc.reset_obs(recs[e], frame)
@@ -107,8 +166,9 @@ def test_raster_matrix_oracle_equals_numpy_and_covers_every_class(geo):
         hx, hy = P.anchor_x - P.hero_w // 2, P.anchor_y - P.hero_w // 2
         inner[hy:hy + P.hero_w, hx:hx + P.hero_w] = 0  # the hero overlay is the only black
         colours.update(np.unique(inner).tolist())
-    print(f"\n{size} x {size}, anchor_y {ay}, crop {P.crop}, {len(recs)} envs:",
-          {k: hist.get(k, 0) for k in EC.ALL_CLASSES})
+        black_envs += bool(np.any(inner == raster_ref.BLACK))
+    print(f"\n{size} x {size}, anchor_y {ay}, crop {P.crop}, pad {P.pad}, {len(recs)} envs:",
+          {k: hist.get(k, 0) for k in EC.ALL_CLASSES}, "bg_differs", bg_differs, "black", black_envs)
     excluded = EXCLUDED[geo]
     for k in EC.ALL_CLASSES:
         if k in excluded:
@@ -120,7 +180,10 @@ def test_raster_matrix_oracle_equals_numpy_and_covers_every_class(geo):
     # the painted content is seen: vehicle, pedestrian, route / green, red, yellow
     for c in (3, 4, 5, 6, 7):
         assert colours[c] >= 3, (geo, c, colours)
-    assert colours[8] == 0  # no black outside the rotated surface: it always covers the output (_ENCLOSED)
+    if "off_surface" in excluded:
+        assert colours[8] == 0  # no black outside the rotated surface: it always covers the output
+    else:
+        assert black_envs >= 3, (geo, black_envs)  # the compose clip is seen: black outside the hero rect
 
 
 @pytest.mark.parametrize("geo", EC.GEOMETRIES, ids=GEO_IDS)
@@ -144,6 +207,35 @@ def test_output_never_leaves_the_crop(geo):
         assert np.all(out == 1), (geo, a, np.unique(out))
         tiles = EC.raster_classes(P, P.map_w / 2.0, P.map_h / 2.0, EC.yaw_of_angle(np.float32(a)))
         assert all(t["fast"] and not t["outside"] and not t["clipped"] for t in tiles), (geo, a)
+
+
+@pytest.mark.parametrize("geo", EC.REDUCED_GEOMETRIES, ids=REDUCED_IDS)
+def test_output_leaves_a_reduced_crop(geo):
+    """The converse for the reduced crops, again from the NumPy restatement alone
+    over the sentinel crop: some heading's frame holds the rotozoom background
+    (a sample outside the crop), and at the off-centre anchors the black outside
+    the rotated surface too; at the centred ones the surface still covers the
+    output (no black). raster_classes agrees heading by heading."""
+    size, ay = geo[:2]
+    P, _, _ = EC.reduced_world(*geo)
+    crop = np.ones((P.crop, P.crop), np.uint8)
+    crop[0, 0] = 2
+    saw_bg = saw_black = 0
+    # every 6 degrees, and the axes with +-0.5 and +-1 degree: the 400-texel crop's
+    # surface misses the output's last rows only within 1.5 degrees of an axis
+    angles = [-87.0 + 6.0 * i for i in range(60)] + [ax + d for ax in (-90.0, 0.0, 90.0, 180.0)
+                                                     for d in (0.0, 0.5, -0.5, 1.0, -1.0)]
+    for a in map(np.float32, angles):
+        out =raster_ref.rotate_compose(P, crop, EC.yaw_of_angle(a), reset=False)
+        # texel (0, 0) itself is sampled by at most two output pixels (a rotation at scale 1): more is background
+        bg = np.count_nonzero(out == 2) > 2
+        tiles = EC.raster_classes(P, P.map_w / 2.0, P.map_h / 2.0, EC.yaw_of_angle(a))
+        assert bool(np.any(out == raster_ref.BLACK)) == any(t["off_surface"] for t in tiles), (geo, a)
+        assert not bg or any(t["outside"] for t in tiles), (geo, a)
+        saw_bg += bg
+        saw_black += bool(np.any(out == raster_ref.BLACK))
+    assert saw_bg >= 3, (geo, saw_bg)
+    assert (saw_black >= 3) if ay != 0.5 else (saw_black == 0), (geo, saw_black)
 
 
 def test_many_actor_case_oracle_equals_numpy():

@@ -19,8 +19,8 @@ torch = pytest.importorskip("torch")
 
 import edge_cases as EC
 from carlabev_env_amd import layout as LY
-from carlabev_env_amd._lib import lib
-from test_gpu_parity import run_parity
+from carlabev_env_amd._lib import check, lib
+from test_gpu_parity import DevWorld, _cached_bank_frames_match_render, error_flags, ptr, run_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +35,120 @@ def test_raster_matrix(geo):
     nothing pressed (the pose stays), a step with gas."""
     P, padded, caps, recs, layout, acts = EC.raster_batch(*geo)
     _run(P, padded, caps, recs, acts)
+
+
+REDUCED_IDS = [EC.reduced_id(g) for g in EC.REDUCED_GEOMETRIES]
+
+
+def _reduced_batch(geo):
+    P, padded, _ = EC.reduced_world(*geo)
+    return EC.raster_batch(*geo[:2], world=(P, padded))
+
+
+@pytest.mark.parametrize("geo", EC.REDUCED_GEOMETRIES, ids=REDUCED_IDS)
+def test_raster_matrix_reduced_crop(geo):
+    """The same matrix under a crop smaller than the reference's (any crop in
+    [size, 400] is accepted): the rotated surface misses part of the output and
+    samples leave the crop, so most envs take tile_out_check (black outside the
+    surface, crop_background's painted corner, windows clipped by the crop, r90
+    on the checked path), through k_ego's RS_FAST word in the steps and through
+    raster_job<RESET> in the reset. Sizes 128 and 256 run the split step."""
+    P, padded, caps, recs, layout, acts = _reduced_batch(geo)
+    _run(P, padded, caps, recs, acts)
+
+
+def test_reduced_crop_fov_masked():
+    """overlay16's corner mask after tile_out_check (every env at this geometry)."""
+    P, padded, caps, recs, layout, acts = _reduced_batch((128, 0.2, 150, 241))
+    _run(P, padded, caps, recs, acts, fov=True)
+
+
+@pytest.mark.parametrize("geo", [(64, 0.2, 70, 119), (128, 0.2, 150, 241)], ids=["64-crop70", "128-crop150"])
+def test_reduced_crop_bank_frames_match_render(geo):
+    """k_bank_frames, cbev_reset_frames and cbev_reset into a 4-slot ring (nout = 4
+    in tile_out_check) where every reset frame takes the checked path, against
+    each other and against the oracle's reset frames."""
+    P, padded, caps, recs, layout, _ = _reduced_batch(geo)
+    _cached_bank_frames_match_render(P, padded, caps, np.ascontiguousarray(recs[0::7][:48]),
+                                     np.ascontiguousarray(recs[3::40][:9]), 4)
+
+
+def test_reduced_crop_split_equals_unsplit_bitwise():
+    """tile_out_check shares k_raster's launch with the tail workgroups of the
+    split step: the matrix's two steps at (128, 0.5, crop 128) in two contexts,
+    unsplit and split, frames, records and outputs equal bit for bit."""
+    P, padded, caps, recs, layout, acts = _reduced_batch((128, 0.5, 128, 128))
+    n, S, L = len(recs), P.size, lib()
+    out = []
+    for split in (0, 1):
+        dw = DevWorld(P, padded, caps)
+        check(L.cbev_set_split_step(dw.ctx, split), "split_step")
+        d_recs = torch.from_numpy(recs.copy()).cuda()
+        frames = torch.zeros((n, S, S), dtype=torch.uint8, device="cuda")
+        check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(frames), 1, None), "reset")
+        b = dict(rew=torch.zeros(n, dtype=torch.float64, device="cuda"),
+                 term=torch.zeros(n, dtype=torch.uint8, device="cuda"),
+                 trunc=torch.zeros(n, dtype=torch.uint8, device="cuda"),
+                 cause=torch.zeros(n, dtype=torch.int32, device="cuda"),
+                 info=torch.zeros((n, 16), dtype=torch.float32, device="cuda"))
+        out.append((dw, d_recs, frames, b))
+    (dA, rA, fA, bA), (dB, rB, fB, bB) = out
+    torch.cuda.synchronize()
+    assert torch.equal(fA, fB), "reset frames"
+    for t in range(len(acts)):
+        a = torch.from_numpy(np.ascontiguousarray(acts[t])).cuda()
+        for dw, d_recs, frames, b in out:
+            check(L.cbev_step(dw.ctx, ptr(d_recs), n, ptr(a), ptr(frames), ptr(b["rew"]), ptr(b["term"]), ptr(b["trunc"]),
+                              ptr(b["cause"]), ptr(b["info"]), None), "step")
+        torch.cuda.synchronize()
+        assert torch.equal(fA, fB), (t, "frames")
+        assert torch.equal(rA, rB), (t, "records")
+        for k in bA:
+            assert torch.equal(bA[k], bB[k]), (t, k)
+    assert error_flags(dA.ctx) == 0 and error_flags(dB.ctx) == 0
+
+
+def _create(P):
+    L = lib()
+    ctx = ctypes.c_void_p()
+    rc = L.cbev_create(ctypes.byref(P), ctypes.byref(EC.CAPS_RASTER.c()), 0, ctypes.byref(ctx))
+    return rc, ctx, L.cbev_last_error()
+
+
+@pytest.mark.parametrize("size", [64, 128, 256])
+def test_crop_range_at_create(size):
+    """crop = size - 1 is refused with a message naming it; the ends of the
+    accepted range, size and 400, create and destroy (nothing is launched)."""
+    P0, _, _ = EC.authored_world(size, 0.5)
+    P = type(P0).from_buffer_copy(P0)
+    P.crop = size - 1
+    rc, ctx, msg = _create(P)
+    assert rc != 0 and f"crop {size - 1}".encode() in msg and not ctx.value
+    for crop in (size, 400):
+        P.crop = crop
+        rc, ctx, msg = _create(P)
+        assert rc == 0 and ctx.value, (crop, msg)
+        lib().cbev_destroy(ctx)
+
+
+def test_render_surface_below_crop_is_refused():
+    """A render surface narrower or lower than the crop (d_crop_origin would
+    clamp its maximum to 0 and the staging read a crop-wide window from a
+    smaller map): refused at cbev_create, each axis alone."""
+    P0, _, _ = EC.authored_world(128, 0.5)
+    for mw, mh in ((100, 1280), (1024, 100)):
+        P = type(P0).from_buffer_copy(P0)
+        P.pad, P.crop = 10, 128
+        P.map_w, P.map_h = mw, mh
+        P.render_w, P.render_h = mw + 2 * P.pad, mh + 2 * P.pad
+        P.map_pitch = (P.render_w + 63) // 64 * 64
+        rc, ctx, msg = _create(P)
+        assert rc != 0 and b"smaller than crop 128" in msg and not ctx.value, msg
+    P.map_w = P.map_h = 108  # render 128 x 128 = the crop: accepted
+    P.render_w = P.render_h = P.map_pitch = 128
+    rc, ctx, msg = _create(P)
+    assert rc == 0 and ctx.value, msg
+    lib().cbev_destroy(ctx)
 
 
 def test_crop_above_400_is_refused():
