@@ -3667,106 +3667,23 @@ struct Lut16 {
 //   FUSE 2  WeightedVehicleHistoryWrapper: the newest frame's channels without the
 //           vehicle channel, then clip(1*v_t + 0.5*v_t-1 + 0.25*v_t-2, 0, 1) summed
 //           in float32 in that order (rgb_to_semantic.py:169-191, 304-332)
-// V pixels per thread (4: float4 stores; 1 when S*S is not a multiple of 4).
+// Every value of a semantic observation is 0 or 1 (FUSE 2's last channel: a
+// multiple of 0.25), so the narrower wire types are lossless:
+//   T = float     float[n][Cout][h][w], 4 pixels per thread (one dword ring load)
+//   T = _Float16  __half[n][Cout][h][w], 8 pixels per thread
+//   T = uint8_t   uint8[n][Cout][h][w] (FUSE 0 / 1), 16 pixels per thread
+// V pixels per thread: 16 bytes / sizeof(T), one 16-byte store per channel, or
+// V = 1, the byte-granular path (h*w not a multiple of the wide V, or pointers
+// that are not 16-byte aligned).
 // Outputs are streamed (non-temporal): the stack is written once per step and
 // read by the learner later, so it should not evict the map and records from L2.
 typedef float nt_f4 __attribute__((ext_vector_type(4)));
+typedef _Float16 nt_h8 __attribute__((ext_vector_type(8)));
 typedef uint32_t nt_u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t nt_u2 __attribute__((ext_vector_type(2)));
 
 template <int V>
-__device__ __forceinline__ void store_nt(float* d, const float* v) {
-  if (V == 4) {
-    nt_f4 x = {v[0], v[V > 1 ? 1 : 0], v[V > 2 ? 2 : 0], v[V > 3 ? 3 : 0]};
-    __builtin_nontemporal_store(x, (nt_f4*)d);
-  } else {
-    __builtin_nontemporal_store(v[0], d);
-  }
-}
-
-template <int V>
 __device__ __forceinline__ void load_masks(const uint8_t* src, const Lut16& lut, uint32_t* m) {
-  if (V == 4) {
-    const uint32_t ids = *(const uint32_t*)src;
-#pragma unroll
-    for (int k = 0; k < V; ++k) m[k] = lut.v[(ids >> (8 * k)) & 15];
-  } else {
-    m[0] = lut.v[src[0] & 15];
-  }
-}
-
-template <int FUSE, int V>
-__global__ __launch_bounds__(256) void k_expand_semantic(const uint8_t* __restrict__ ring, int n, int F, int head, int C,
-                                                         int vidx, int SS, Lut16 lut, float* __restrict__ out) {
-  const int nv = SS / V;
-  const int Cout = FUSE == 0 ? F * C : (FUSE == 1 ? C + 2 : C);
-  const int64_t total = (int64_t)n * nv;
-  for (int64_t q = blockIdx.x * 256ll + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
-    const int64_t e = q / nv;
-    const int64_t p = (q - e * nv) * V;
-    float* o = out + e * Cout * (int64_t)SS + p;
-    float vals[V];
-    if (FUSE == 0) {
-      for (int f = 0; f < F; ++f) {  // oldest -> newest
-        const int slot = (head + 1 + f) % F;
-        uint32_t m[V];
-        load_masks<V>(ring + ((int64_t)slot * n + e) * SS + p, lut, m);
-        for (int c = 0; c < C; ++c) {
-#pragma unroll
-          for (int k = 0; k < V; ++k) vals[k] = (float)((m[k] >> c) & 1);
-          store_nt<V>(o + (int64_t)(f * C + c) * SS, vals);
-        }
-      }
-    } else {
-      uint32_t m0[V], m1[V], m2[V];  // newest, newest-1, newest-2
-      load_masks<V>(ring + ((int64_t)head * n + e) * SS + p, lut, m0);
-      load_masks<V>(ring + ((int64_t)((head - 1 + F) % F) * n + e) * SS + p, lut, m1);
-      load_masks<V>(ring + ((int64_t)((head - 2 + 2 * F) % F) * n + e) * SS + p, lut, m2);
-      int oc = 0;
-      for (int c = 0; c < C; ++c) {  // static channels of the newest frame
-        if (c == vidx) continue;
-#pragma unroll
-        for (int k = 0; k < V; ++k) vals[k] = (float)((m0[k] >> c) & 1);
-        store_nt<V>(o + (int64_t)(oc++) * SS, vals);
-      }
-      float v0[V], v1[V], v2[V];
-#pragma unroll
-      for (int k = 0; k < V; ++k) {
-        v0[k] = (float)((m0[k] >> vidx) & 1);
-        v1[k] = (float)((m1[k] >> vidx) & 1);
-        v2[k] = (float)((m2[k] >> vidx) & 1);
-      }
-      if (FUSE == 1) {
-        store_nt<V>(o + (int64_t)oc * SS, v0);
-        store_nt<V>(o + (int64_t)(oc + 1) * SS, v1);
-        store_nt<V>(o + (int64_t)(oc + 2) * SS, v2);
-      } else {
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-          float acc = 0.0f;
-          acc += 1.0f * v0[k];
-          acc += 0.5f * v1[k];
-          acc += 0.25f * v2[k];
-          vals[k] = fminf(fmaxf(acc, 0.0f), 1.0f);
-        }
-        store_nt<V>(o + (int64_t)oc * SS, vals);
-      }
-    }
-  }
-}
-
-// ---- compact wire types of the semantic expansion (cbev_expand_obs_typed) ----
-// The same ring, Lut16 channel masks, FUSE kinds and channel order as
-// k_expand_semantic; every value of a semantic observation is 0 or 1 (FUSE 2's
-// last channel: a multiple of 0.25), so the narrower types are lossless:
-//   T = _Float16  __half[n][Cout][h][w], 8 pixels per thread and 16-byte store
-//   T = uint8_t   uint8[n][Cout][h][w] (FUSE 0 / 1), 16 pixels per 16-byte store
-// V = 1 is the byte-granular path (h*w not a multiple of 16 / sizeof(T), or
-// pointers that are not 16-byte aligned). Stores are streamed as above.
-typedef _Float16 nt_h8 __attribute__((ext_vector_type(8)));
-
-template <int V>
-__device__ __forceinline__ void load_masks_w(const uint8_t* src, const Lut16& lut, uint32_t* m) {
   if constexpr (V == 1) {
     m[0] = lut.v[src[0] & 15];
   } else {
@@ -3774,9 +3691,11 @@ __device__ __forceinline__ void load_masks_w(const uint8_t* src, const Lut16& lu
     if constexpr (V == 16) {
       const uint4 x = *(const uint4*)src;
       w[0] = x.x, w[1] = x.y, w[2] = x.z, w[3] = x.w;
-    } else {
+    } else if constexpr (V == 8) {
       const uint2 x = *(const uint2*)src;
       w[0] = x.x, w[1] = x.y;
+    } else {
+      w[0] = *(const uint32_t*)src;
     }
 #pragma unroll
     for (int k = 0; k < V; ++k) m[k] = lut.v[(w[k >> 2] >> (8 * (k & 3))) & 15];
@@ -3784,9 +3703,12 @@ __device__ __forceinline__ void load_masks_w(const uint8_t* src, const Lut16& lu
 }
 
 template <typename T, int V>
-__device__ __forceinline__ void store_ntw(T* d, const T* v) {
+__device__ __forceinline__ void store_nt(T* d, const T* v) {
   if constexpr (V == 1) {
     __builtin_nontemporal_store(v[0], d);
+  } else if constexpr (sizeof(T) == 4) {
+    nt_f4 x = {v[0], v[1], v[2], v[3]};
+    __builtin_nontemporal_store(x, (nt_f4*)d);
   } else if constexpr (sizeof(T) == 2) {
     nt_h8 x;
 #pragma unroll
@@ -3803,8 +3725,8 @@ __device__ __forceinline__ void store_ntw(T* d, const T* v) {
 }
 
 template <int FUSE, typename T, int V>
-__global__ __launch_bounds__(256) void k_expand_semantic_w(const uint8_t* __restrict__ ring, int n, int F, int head, int C,
-                                                           int vidx, int SS, Lut16 lut, T* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_expand_semantic(const uint8_t* __restrict__ ring, int n, int F, int head, int C,
+                                                         int vidx, int SS, Lut16 lut, T* __restrict__ out) {
   const int nv = SS / V;
   const int Cout = FUSE == 0 ? F * C : (FUSE == 1 ? C + 2 : C);
   const int64_t total = (int64_t)n * nv;
@@ -3817,35 +3739,35 @@ __global__ __launch_bounds__(256) void k_expand_semantic_w(const uint8_t* __rest
       for (int f = 0; f < F; ++f) {  // oldest -> newest
         const int slot = (head + 1 + f) % F;
         uint32_t m[V];
-        load_masks_w<V>(ring + ((int64_t)slot * n + e) * SS + p, lut, m);
+        load_masks<V>(ring + ((int64_t)slot * n + e) * SS + p, lut, m);
         for (int c = 0; c < C; ++c) {
 #pragma unroll
           for (int k = 0; k < V; ++k) vals[k] = (T)((m[k] >> c) & 1);
-          store_ntw<T, V>(o + (int64_t)(f * C + c) * SS, vals);
+          store_nt<T, V>(o + (int64_t)(f * C + c) * SS, vals);
         }
       }
     } else {
       uint32_t m0[V], m1[V], m2[V];  // newest, newest-1, newest-2
-      load_masks_w<V>(ring + ((int64_t)head * n + e) * SS + p, lut, m0);
-      load_masks_w<V>(ring + ((int64_t)((head - 1 + F) % F) * n + e) * SS + p, lut, m1);
-      load_masks_w<V>(ring + ((int64_t)((head - 2 + 2 * F) % F) * n + e) * SS + p, lut, m2);
+      load_masks<V>(ring + ((int64_t)head * n + e) * SS + p, lut, m0);
+      load_masks<V>(ring + ((int64_t)((head - 1 + F) % F) * n + e) * SS + p, lut, m1);
+      load_masks<V>(ring + ((int64_t)((head - 2 + 2 * F) % F) * n + e) * SS + p, lut, m2);
       int oc = 0;
       for (int c = 0; c < C; ++c) {  // static channels of the newest frame
         if (c == vidx) continue;
 #pragma unroll
         for (int k = 0; k < V; ++k) vals[k] = (T)((m0[k] >> c) & 1);
-        store_ntw<T, V>(o + (int64_t)(oc++) * SS, vals);
+        store_nt<T, V>(o + (int64_t)(oc++) * SS, vals);
       }
       if (FUSE == 1) {
 #pragma unroll
         for (int k = 0; k < V; ++k) vals[k] = (T)((m0[k] >> vidx) & 1);
-        store_ntw<T, V>(o + (int64_t)oc * SS, vals);
+        store_nt<T, V>(o + (int64_t)oc * SS, vals);
 #pragma unroll
         for (int k = 0; k < V; ++k) vals[k] = (T)((m1[k] >> vidx) & 1);
-        store_ntw<T, V>(o + (int64_t)(oc + 1) * SS, vals);
+        store_nt<T, V>(o + (int64_t)(oc + 1) * SS, vals);
 #pragma unroll
         for (int k = 0; k < V; ++k) vals[k] = (T)((m2[k] >> vidx) & 1);
-        store_ntw<T, V>(o + (int64_t)(oc + 2) * SS, vals);
+        store_nt<T, V>(o + (int64_t)(oc + 2) * SS, vals);
       } else {
 #pragma unroll
         for (int k = 0; k < V; ++k) {  // float32 in the reference's order, clipped, then converted
@@ -3855,7 +3777,7 @@ __global__ __launch_bounds__(256) void k_expand_semantic_w(const uint8_t* __rest
           acc += 0.25f * (float)((m2[k] >> vidx) & 1);
           vals[k] = (T)fminf(fmaxf(acc, 0.0f), 1.0f);
         }
-        store_ntw<T, V>(o + (int64_t)oc * SS, vals);
+        store_nt<T, V>(o + (int64_t)oc * SS, vals);
       }
     }
   }
@@ -3954,61 +3876,6 @@ __global__ __launch_bounds__(256) void k_expand_semantic_bits(const uint8_t* __r
     }
   }
 }
-
-#ifdef CBEV_BITS_BALLOT
-// The measured alternative of the V = 32 path ("Compact wire
-// observations"): a wave takes 256 pixels, lane l loads pixels 64r + l, one
-// __ballot per (r, channel) yields 64 pixels of a plane, and lanes 0..7 store
-// the four ballot words as 8 dwords. h*w a multiple of 256.
-template <int FUSE>
-__global__ __launch_bounds__(256) void k_expand_semantic_ballot(const uint8_t* __restrict__ ring, int n, int F, int head,
-                                                                int C, int vidx, int SS, Lut16 lut,
-                                                                uint8_t* __restrict__ out) {
-  const int PB = SS >> 3, nv = SS >> 8;
-  const int lane = threadIdx.x & 63;
-  const int Cout = FUSE == 0 ? F * C : C + 2;
-  const int64_t total = (int64_t)n * nv;
-  auto emit = [&](uint8_t* d, const uint32_t* m, int c) {
-    uint64_t b[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) b[r] = __ballot((m[r] >> c) & 1u);
-    const int r = lane >> 1;
-    const uint64_t x = r == 0 ? b[0] : (r == 1 ? b[1] : (r == 2 ? b[2] : b[3]));
-    const uint32_t w = (lane & 1) ? (uint32_t)(x >> 32) : (uint32_t)x;
-    if (lane < 8) __builtin_nontemporal_store(w, (uint32_t*)d + lane);
-  };
-  auto load = [&](int slot, int64_t e, int p, uint32_t* m) {
-    const uint8_t* src = ring + ((int64_t)slot * n + e) * SS + p + lane;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) m[r] = lut.v[src[64 * r] & 15];
-  };
-  for (int64_t q = blockIdx.x * 4ll + (threadIdx.x >> 6); q < total; q += (int64_t)gridDim.x * 4) {
-    const int64_t e = q / nv;
-    const int j = (int)(q - e * nv);
-    uint8_t* o = out + e * Cout * (int64_t)PB + j * 32;
-    uint32_t m[4];
-    if (FUSE == 0) {
-      for (int f = 0; f < F; ++f) {
-        load((head + 1 + f) % F, e, j * 256, m);
-        for (int c = 0; c < C; ++c) emit(o + (int64_t)(f * C + c) * PB, m, c);
-      }
-    } else {
-      uint32_t m1[4], m2[4];
-      load(head, e, j * 256, m);
-      load((head - 1 + F) % F, e, j * 256, m1);
-      load((head - 2 + 2 * F) % F, e, j * 256, m2);
-      int oc = 0;
-      for (int c = 0; c < C; ++c) {
-        if (c == vidx) continue;
-        emit(o + (int64_t)(oc++) * PB, m, c);
-      }
-      emit(o + (int64_t)oc * PB, m, vidx);
-      emit(o + (int64_t)(oc + 1) * PB, m1, vidx);
-      emit(o + (int64_t)(oc + 2) * PB, m2, vidx);
-    }
-  }
-}
-#endif
 
 // The learner's side of the bit-packed planes: packed uint8[rows][ceil(P / 8)]
 // -> T[rows][P] (float32, float16 or uint8 0 / 1). WIDE (P a multiple of 8,
@@ -4517,6 +4384,14 @@ static uint32_t bank_stride(int n_bank) {
   uint32_t p = (uint32_t)(0.6180339887498949 * (double)n_bank) | 1u;
   while (gcd_u32(p, (uint32_t)n_bank) != 1u) p += 2u;
   return p % (uint32_t)n_bank;
+}
+
+// One launch of a semantic expansion kernel (k_expand_semantic, k_expand_semantic_bits); T from the kernel
+template <typename T>
+static void launch_sem(void (*k)(const uint8_t*, int, int, int, int, int, int, Lut16, T*), int grid, void* stream,
+                       const uint8_t* ring, int n, int F, int head, int C, int vidx, int SS, const Lut16& lut,
+                       void* out) {
+  hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, (hipStream_t)stream, ring, n, F, head, C, vidx, SS, lut, (T*)out);
 }
 
 
@@ -5117,18 +4992,18 @@ int cbev_reset_counts(cbev_ctx* c, uint32_t* counts_host, int n) {
 
 int cbev_bank_stride(int n_bank) { return n_bank > 0 ? (int)bank_stride(n_bank) : -1; }
 
-int cbev_expand_obs(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int head, int kind, int n_channels,
-                    const uint32_t* lut_host, void* out, void* stream) {
-  if (!c || !ring || !out) return set_err(CBEV_EINVAL, "null argument");
+// The semantic kinds (0, 3, 4) of cbev_expand_obs and cbev_expand_obs_typed, to
+// any wire type: the checks, the choice of kernel and the launch.
+static int expand_semantic(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int head, int kind, int n_channels,
+                           const uint32_t* lut_host, int out_dtype, void* out, void* stream) {
   CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
-  if (!lut_host && kind != 5) return set_err(CBEV_EINVAL, "null lut");
+  if (!lut_host) return set_err(CBEV_EINVAL, "null lut");
   if (n_frames < 1 || head < 0 || head >= n_frames) return set_err(CBEV_EINVAL, "bad frame ring");
-  const bool sem = kind == 0 || kind == 3 || kind == 4;
-  if (sem && (n_channels < 1 || n_channels > 16)) return set_err(CBEV_EINVAL, "bad channel count");
+  if (n_channels < 1 || n_channels > 16) return set_err(CBEV_EINVAL, "bad channel count");
   Lut16 lut{};
-  if (lut_host) memcpy(lut.v, lut_host, sizeof lut.v);
+  memcpy(lut.v, lut_host, sizeof lut.v);
   int vidx = -1;
-  if (kind == 3 || kind == 4) {
+  if (kind != 0) {
     // the vehicle channel is the one bit the vehicle colour sets (vehicle_channel_index,
     // rgb_to_semantic.py:55-62); the fusions keep 3 frames (:152-191)
     const uint32_t vm = lut.v[CBEV_PX_VEHICLE];
@@ -5138,38 +5013,57 @@ int cbev_expand_obs(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int h
     if (n_frames < 3) return set_err(CBEV_EINVAL, "vehicle history fusion requires frame_stack >= 3");
   }
   if (n <= 0) return CBEV_OK;
+  const int SS = c->obs_h * c->obs_w;
+  // V pixels per thread: the wide kernel (16 bytes of an element type, 32 pixels
+  // of bits) where the pixel count and the pointers allow it, else the narrow one
+  const bool bits = out_dtype == CBEV_OBS_BITS;
+  const int VW = bits ? 32 : out_dtype == CBEV_OBS_U8 ? 16 : out_dtype == CBEV_OBS_F16 ? 8 : 4;
+  const bool wide = ((((uintptr_t)ring) | ((uintptr_t)out)) & 15) == 0 && SS % VW == 0;
+  const int V = wide ? VW : (bits ? 8 : 1);
+  const int64_t threads = (int64_t)n * ((SS + V - 1) / V);
+  const int grid = (int)std::min<int64_t>((threads + 255) / 256, 4096);
+  const auto launch = [&](auto wide_k, decltype(wide_k) narrow_k) {
+    launch_sem(wide ? wide_k : narrow_k, grid, stream, ring, n, n_frames, head, n_channels, vidx, SS, lut, out);
+  };
+  // 4 * FUSE + wire type; FUSE 2 to uint8 or bits is refused by cbev_expand_obs_typed
+  switch (4 * (kind == 0 ? 0 : kind == 3 ? 1 : 2) + out_dtype) {
+    case 0 + CBEV_OBS_F32: launch(k_expand_semantic<0, float, 4>, k_expand_semantic<0, float, 1>); break;
+    case 0 + CBEV_OBS_F16: launch(k_expand_semantic<0, _Float16, 8>, k_expand_semantic<0, _Float16, 1>); break;
+    case 0 + CBEV_OBS_U8: launch(k_expand_semantic<0, uint8_t, 16>, k_expand_semantic<0, uint8_t, 1>); break;
+    case 0 + CBEV_OBS_BITS: launch(k_expand_semantic_bits<0, 32>, k_expand_semantic_bits<0, 8>); break;
+    case 4 + CBEV_OBS_F32: launch(k_expand_semantic<1, float, 4>, k_expand_semantic<1, float, 1>); break;
+    case 4 + CBEV_OBS_F16: launch(k_expand_semantic<1, _Float16, 8>, k_expand_semantic<1, _Float16, 1>); break;
+    case 4 + CBEV_OBS_U8: launch(k_expand_semantic<1, uint8_t, 16>, k_expand_semantic<1, uint8_t, 1>); break;
+    case 4 + CBEV_OBS_BITS: launch(k_expand_semantic_bits<1, 32>, k_expand_semantic_bits<1, 8>); break;
+    case 8 + CBEV_OBS_F32: launch(k_expand_semantic<2, float, 4>, k_expand_semantic<2, float, 1>); break;
+    case 8 + CBEV_OBS_F16: launch(k_expand_semantic<2, _Float16, 8>, k_expand_semantic<2, _Float16, 1>); break;
+    default: return set_err(CBEV_EINVAL, "no semantic expansion of kind %d to obs dtype %d", kind, out_dtype);
+  }
+  HIP_TRY(hipGetLastError());
+  return CBEV_OK;
+}
+
+int cbev_expand_obs(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int head, int kind, int n_channels,
+                    const uint32_t* lut_host, void* out, void* stream) {
+  if (!c || !ring || !out) return set_err(CBEV_EINVAL, "null argument");
+  if (kind == 0 || kind == 3 || kind == 4)
+    return expand_semantic(c, ring, n, n_frames, head, kind, n_channels, lut_host, CBEV_OBS_F32, out, stream);
+  CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
+  if (!lut_host && kind != 5) return set_err(CBEV_EINVAL, "null lut");
+  if (n_frames < 1 || head < 0 || head >= n_frames) return set_err(CBEV_EINVAL, "bad frame ring");
+  Lut16 lut{};
+  if (lut_host) memcpy(lut.v, lut_host, sizeof lut.v);
+  if (n <= 0) return CBEV_OK;
   hipStream_t s = (hipStream_t)stream;
   const int SS = c->obs_h * c->obs_w;
   const int grid = 4096;
-  const bool v4 = SS % 4 == 0, v16 = SS % 16 == 0;
+  const bool v16 = SS % 16 == 0;
   switch (kind) {
-#define SEM_CASE(K, FUSE)                                                                                          \
-  case K:                                                                                                          \
-    if (v4)                                                                                                        \
-      hipLaunchKernelGGL((k_expand_semantic<FUSE, 4>), dim3(grid), dim3(256), 0, s, ring, n, n_frames, head,        \
-                         n_channels, vidx, SS, lut, (float*)out);                                                   \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_expand_semantic<FUSE, 1>), dim3(grid), dim3(256), 0, s, ring, n, n_frames, head,        \
-                         n_channels, vidx, SS, lut, (float*)out);                                                   \
-    break;
-    SEM_CASE(0, 0)
-    SEM_CASE(3, 1)
-    SEM_CASE(4, 2)
-#undef SEM_CASE
     case 1:
     case 5:
-      if (v16 && kind == 1)
-        hipLaunchKernelGGL((k_expand_gray<false, 16>), dim3(grid), dim3(256), 0, s, ring, n, n_frames, head, SS, lut,
-                           (uint8_t*)out);
-      else if (v16)
-        hipLaunchKernelGGL((k_expand_gray<true, 16>), dim3(grid), dim3(256), 0, s, ring, n, n_frames, head, SS, lut,
-                           (uint8_t*)out);
-      else if (kind == 1)
-        hipLaunchKernelGGL((k_expand_gray<false, 1>), dim3(grid), dim3(256), 0, s, ring, n, n_frames, head, SS, lut,
-                           (uint8_t*)out);
-      else
-        hipLaunchKernelGGL((k_expand_gray<true, 1>), dim3(grid), dim3(256), 0, s, ring, n, n_frames, head, SS, lut,
-                           (uint8_t*)out);
+      hipLaunchKernelGGL(kind == 1 ? (v16 ? k_expand_gray<false, 16> : k_expand_gray<false, 1>)
+                                   : (v16 ? k_expand_gray<true, 16> : k_expand_gray<true, 1>),
+                         dim3(grid), dim3(256), 0, s, ring, n, n_frames, head, SS, lut, (uint8_t*)out);
       break;
     case 2:
       hipLaunchKernelGGL(k_expand_rgb, dim3(grid), dim3(256), 0, s, ring, n, head, c->P.size * c->P.size, lut,
@@ -5194,85 +5088,9 @@ int cbev_expand_obs_typed(cbev_ctx* c, const uint8_t* ring, int n, int n_frames,
   }
   if (kind == 4 && (out_dtype == CBEV_OBS_U8 || out_dtype == CBEV_OBS_BITS))
     return set_err(CBEV_EINVAL, "the weighted vehicle history is fractional: obs dtype %d cannot hold it", out_dtype);
-  if (out_dtype == CBEV_OBS_F32 || !(kind == 0 || kind == 3 || kind == 4))
+  if (!(kind == 0 || kind == 3 || kind == 4))  // refused there as an unknown kind
     return cbev_expand_obs(c, ring, n, n_frames, head, kind, n_channels, lut_host, out, stream);
-  CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
-  if (!lut_host) return set_err(CBEV_EINVAL, "null lut");
-  if (n_frames < 1 || head < 0 || head >= n_frames) return set_err(CBEV_EINVAL, "bad frame ring");
-  if (n_channels < 1 || n_channels > 16) return set_err(CBEV_EINVAL, "bad channel count");
-  Lut16 lut{};
-  memcpy(lut.v, lut_host, sizeof lut.v);
-  int vidx = -1;
-  if (kind != 0) {  // as cbev_expand_obs
-    const uint32_t vm = lut.v[CBEV_PX_VEHICLE];
-    if (vm == 0 || (vm & (vm - 1)) != 0 || vm >= (1u << n_channels))
-      return set_err(CBEV_EINVAL, "vehicle history fusion needs a semantic mode with a vehicle channel");
-    vidx = __builtin_ctz(vm);
-    if (n_frames < 3) return set_err(CBEV_EINVAL, "vehicle history fusion requires frame_stack >= 3");
-  }
-  if (n <= 0) return CBEV_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int SS = c->obs_h * c->obs_w;
-  const bool al16 = ((((uintptr_t)ring) | ((uintptr_t)out)) & 15) == 0;
-  // V pixels per thread: the widest the pixel count and the pointers allow
-  const int V = out_dtype == CBEV_OBS_F16 ? (al16 && SS % 8 == 0 ? 8 : 1)
-                : out_dtype == CBEV_OBS_U8 ? (al16 && SS % 16 == 0 ? 16 : 1)
-                                           : (al16 && SS % 32 == 0 ? 32 : 8);
-  const int64_t threads = (int64_t)n * ((SS + V - 1) / V);
-  const int grid = (int)std::min<int64_t>((threads + 255) / 256, 4096);
-#define TYPED_LAUNCH(KERNEL, OUT_T)                                                                               \
-  hipLaunchKernelGGL((KERNEL), dim3(grid), dim3(256), 0, s, ring, n, n_frames, head, n_channels, vidx, SS, lut, \
-                     (OUT_T*)out)
-#ifdef CBEV_BITS_BALLOT
-#define BITS_WIDE_LAUNCH(FUSE)                                 \
-  do {                                                         \
-    if (SS % 256 == 0) {                                       \
-      TYPED_LAUNCH((k_expand_semantic_ballot<FUSE>), uint8_t); \
-    } else {                                                   \
-      TYPED_LAUNCH((k_expand_semantic_bits<FUSE, 32>), uint8_t); \
-    }                                                          \
-  } while (0)
-#else
-#define BITS_WIDE_LAUNCH(FUSE) TYPED_LAUNCH((k_expand_semantic_bits<FUSE, 32>), uint8_t)
-#endif
-#define TYPED_FUSE(FUSE)                                                \
-  switch (out_dtype) {                                                  \
-    case CBEV_OBS_F16:                                                  \
-      if (V == 8) {                                                     \
-        TYPED_LAUNCH((k_expand_semantic_w<FUSE, _Float16, 8>), _Float16); \
-      } else {                                                          \
-        TYPED_LAUNCH((k_expand_semantic_w<FUSE, _Float16, 1>), _Float16); \
-      }                                                                 \
-      break;                                                            \
-    case CBEV_OBS_U8:                                                   \
-      if (V == 16) {                                                    \
-        TYPED_LAUNCH((k_expand_semantic_w<FUSE, uint8_t, 16>), uint8_t); \
-      } else {                                                          \
-        TYPED_LAUNCH((k_expand_semantic_w<FUSE, uint8_t, 1>), uint8_t); \
-      }                                                                 \
-      break;                                                            \
-    default:                                                            \
-      if (V == 32) {                                                    \
-        BITS_WIDE_LAUNCH(FUSE);                                         \
-      } else {                                                          \
-        TYPED_LAUNCH((k_expand_semantic_bits<FUSE, 8>), uint8_t);       \
-      }                                                                 \
-      break;                                                            \
-  }
-  if (kind == 0) {
-    TYPED_FUSE(0)
-  } else if (kind == 3) {
-    TYPED_FUSE(1)
-  } else if (V == 8) {  // kind 4: float16 only (refused above otherwise)
-    TYPED_LAUNCH((k_expand_semantic_w<2, _Float16, 8>), _Float16);
-  } else {
-    TYPED_LAUNCH((k_expand_semantic_w<2, _Float16, 1>), _Float16);
-  }
-#undef BITS_WIDE_LAUNCH
-#undef TYPED_FUSE
-#undef TYPED_LAUNCH
-  HIP_TRY(hipGetLastError());
-  return CBEV_OK;
+  return expand_semantic(c, ring, n, n_frames, head, kind, n_channels, lut_host, out_dtype, out, stream);
 }
 
 int cbev_unpack_obs(cbev_ctx* c, const uint8_t* packed, int rows, int pixels, int out_dtype, void* out, void* stream) {

@@ -233,10 +233,11 @@ int cbev_set_split_step(cbev_ctx* ctx, int on);
 int cbev_expand_obs(cbev_ctx* ctx, const uint8_t* ring, int n, int n_frames, int head, int kind, int n_channels,
                     const uint32_t* channel_lut_host, void* out, void* stream);
 
-/* Compact wire types of the semantic kinds (0, 3, 4). Every value of a semantic
+/* Wire types of the semantic kinds (0, 3, 4). Every value of a semantic
  * observation is 0 or 1 (kind 4's last channel: 0, 0.25, 0.5, 0.75 or 1), so
- * these are lossless; Cout is the channel count of the kind above:
- *   CBEV_OBS_F32   float32[n][Cout][h][w], cbev_expand_obs itself
+ * the compact ones are lossless; Cout is the channel count of the kind above:
+ *   CBEV_OBS_F32   float32[n][Cout][h][w]: what cbev_expand_obs writes, by the
+ *                  same kernel family and host path as the types below
  *   CBEV_OBS_F16   float16[n][Cout][h][w] (kind 4: summed and clipped in float32, then converted)
  *   CBEV_OBS_U8    uint8[n][Cout][h][w], 0 or 1; kinds 0 and 3
  *   CBEV_OBS_BITS  uint8[n][Cout][ceil(h*w / 8)]: pixel p of a channel plane is

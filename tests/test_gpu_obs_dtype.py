@@ -1,5 +1,5 @@
-"""GPU parity of the compact wire types of the semantic observation
-(cbev_expand_obs_typed: float16, uint8, bit-packed; cbev_unpack_obs) against the
+"""GPU parity of the wire types of the semantic observation
+(cbev_expand_obs_typed: float32, float16, uint8, bit-packed; cbev_unpack_obs) against the
 wrapper oracle (oracle/wrappers.py), through the C-ABI, and of the vector env's
 obs_dtype end to end.
 
@@ -29,8 +29,10 @@ P_ = ctypes.c_void_p
 MODES = ("binary", "2-class", "4-class", "5-class", "6-class", "7-class")
 VMODES = ("4-class", "5-class", "6-class", "7-class")
 FUSION = {0: "stack", 3: "vehicle_temporal", 4: "vehicle_weighted"}
-CODES = {"float16": OBS_F16, "uint8": OBS_U8, "bits": OBS_BITS}
-SIZES = [(5, 7), (9, 8), (8, 12), (84, 84), (128, 128)]  # 35, 72, 96, 7056, 16384 pixels
+CODES = {"float32": OBS_F32, "float16": OBS_F16, "uint8": OBS_U8, "bits": OBS_BITS}
+# 35, 36, 72, 96, 7056, 16384 pixels: no multiple of 4; of 4, not 8 (float32 wide, float16 narrow); of 8, not 16;
+# of 32; of 16, not 32; the benchmark's
+SIZES = [(5, 7), (6, 6), (9, 8), (8, 12), (84, 84), (128, 128)]
 GUARD = 64
 N_MAX = 9
 
@@ -57,7 +59,7 @@ def kinds_of(mode):
 
 
 def dtypes_of(kind):
-    return ("float16",) if kind == 4 else ("float16", "uint8", "bits")
+    return ("float32", "float16") if kind == 4 else ("float32", "float16", "uint8", "bits")
 
 
 def cout(kind, F, C):
@@ -66,6 +68,8 @@ def cout(kind, F, C):
 
 def convert(ref: np.ndarray, dt: str) -> np.ndarray:
     """float32[..., C, h, w] (or [..., C, P]) expectation -> the wire type's bytes."""
+    if dt == "float32":
+        return ref.astype(np.float32)
     if dt == "float16":
         return ref.astype(np.float16)
     if dt == "uint8":
@@ -75,7 +79,7 @@ def convert(ref: np.ndarray, dt: str) -> np.ndarray:
 
 
 def out_bytes(dt, n, Cout, P):
-    return n * Cout * {"float16": 2 * P, "uint8": P, "bits": (P + 7) // 8}[dt]
+    return n * Cout * {"float32": 4 * P, "float16": 2 * P, "uint8": P, "bits": (P + 7) // 8}[dt]
 
 
 def typed_expand(c, ring_d, n, F, head, kind, C, lut, dt, Cout, P, offset=0, stream=None, buf=None):
@@ -94,8 +98,8 @@ def typed_expand(c, ring_d, n, F, head, kind, C, lut, dt, Cout, P, offset=0, str
 
 
 def as_wire(raw: np.ndarray, dt, n, Cout, hw):
-    if dt == "float16":
-        return raw.view(np.float16).reshape(n, Cout, *hw)
+    if dt in ("float32", "float16"):
+        return raw.view(dt).reshape(n, Cout, *hw)
     if dt == "uint8":
         return raw.reshape(n, Cout, *hw)
     return raw.reshape(n, Cout, -1)
@@ -145,8 +149,8 @@ def test_typed_expansion_matches_oracle(hw, F, head):
                     raw, intact = typed_expand(c, ring_d, n, F, head, kind, C, lut, dt, Cout, P)
                     want = convert(ref, dt)
                     got = as_wire(raw, dt, n, Cout, hw)
-                    # every output byte is written (0xA5 is no float16 / uint8 value of an
-                    # observation; for bits every byte is compared) and nothing past it
+                    # every output byte is written (0xA5A5A5A5 / 0xA5A5 / 0xA5 is no float32 / float16 /
+                    # uint8 value of an observation; for bits every byte is compared) and nothing past it
                     assert got.shape == want.shape and np.array_equal(got, want), (hw, n, mode, kind, dt)
                     assert intact, (hw, n, mode, kind, dt)
                     if dt == "bits" and P % 8:
@@ -155,7 +159,7 @@ def test_typed_expansion_matches_oracle(hw, F, head):
 
 @pytest.mark.parametrize("hw", [(8, 12), (128, 128)])
 def test_typed_expansion_into_unaligned_output(hw):
-    """An output that is not 16-byte aligned takes the byte-granular kernels."""
+    """An output or a ring that is not 16-byte aligned takes the byte-granular kernels."""
     c = Ctx(hw)
     F, head, mode, P = 4, 1, "6-class", hw[0] * hw[1]
     n = N_MAX if P < 1000 else 2
@@ -165,12 +169,40 @@ def test_typed_expansion_into_unaligned_output(hw):
         ref = oracle_obs(hw, F, head, mode, kind)[:n]
         for dt in dtypes_of(kind):
             raw, intact = typed_expand(c, ring_d, n, F, head, kind, 6, lut, dt, cout(kind, F, 6), P,
-                                       offset=2 if dt == "float16" else 1)
+                                       offset={"float32": 4, "float16": 2}.get(dt, 1))
             assert np.array_equal(as_wire(raw.copy(), dt, n, cout(kind, F, 6), hw), convert(ref, dt)), (kind, dt)
             assert intact, (kind, dt)
+    if hw != (8, 12):
+        return
+    # the ring as a view that starts 1 byte into a device buffer, the output aligned
+    odd = torch.empty((ring_d.numel() + 1,), dtype=torch.uint8, device="cuda")[1:]
+    odd.copy_(ring_d.reshape(-1))
+    assert odd.data_ptr() % 2 == 1
+    for kind in (0, 3):
+        ref = oracle_obs(hw, F, head, mode, kind)[:n]
+        for dt in dtypes_of(kind):
+            raw, intact = typed_expand(c, odd, n, F, head, kind, 6, lut, dt, cout(kind, F, 6), P)
+            assert np.array_equal(as_wire(raw, dt, n, cout(kind, F, 6), hw), convert(ref, dt)), ("ring + 1", kind, dt)
+            assert intact, ("ring + 1", kind, dt)
 
 
 # ------------------------------------------------------------ 2. off-palette, consistency with float32
+def expected_f32(ring_h, head, kind, C, lut):
+    """float32[n][Cout][h][w] from the channel masks alone: bit c of lut[id] per
+    pixel and frame, laid out in the kind's stack order (cbev.h, cbev_expand_obs)."""
+    F = ring_h.shape[0]
+    masks = lut[ring_h[[(head + 1 + f) % F for f in range(F)]]]  # [F][n][h][w], oldest first
+    bits = np.stack([(masks >> c) & 1 for c in range(C)], axis=2).astype(np.float32)  # [F][n][C][h][w]
+    if kind == 0:
+        return bits.transpose(1, 0, 2, 3, 4).reshape(bits.shape[1], F * C, *bits.shape[3:])
+    v = int(lut[3]).bit_length() - 1  # the channel the vehicle id (3) sets
+    static = np.delete(bits[-1], v, axis=1)
+    v0, v1, v2 = bits[-1][:, v], bits[-2][:, v], bits[-3][:, v]
+    if kind == 3:
+        return np.concatenate([static, np.stack([v0, v1, v2], axis=1)], axis=1)
+    return np.concatenate([static, np.clip(v0 + 0.5 * v1 + 0.25 * v2, 0, 1)[:, None]], axis=1)
+
+
 @pytest.mark.parametrize("hw", [(9, 8), (128, 128)])
 def test_typed_equals_float32_expansion_with_off_palette_ids(hw):
     c = Ctx(hw)
@@ -193,6 +225,7 @@ def test_typed_equals_float32_expansion_with_off_palette_ids(hw):
             torch.cuda.synchronize()
             ref = f32.cpu().numpy()
             assert np.array_equal(via.cpu().numpy(), ref)
+            assert np.array_equal(ref, expected_f32(ring_h, head, kind, C, lut)), (mode, kind)
             if mode in MODES and kind != 0:  # id 15 sets no channel: nothing of the newest frame where it is
                 assert lut[OP.OFF_PALETTE] == 0
                 assert not ref[:, :C - 1].transpose(1, 0, 2, 3)[:, ring_h[head] == OP.OFF_PALETTE].any()
