@@ -48,6 +48,8 @@ def lib():
     L.cbev_step.restype = _I
     L.cbev_step_repeat.argtypes = [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]
     L.cbev_step_repeat.restype = _I
+    L.cbev_step_masked.argtypes = [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]
+    L.cbev_step_masked.restype = _I
     L.cbev_reset.argtypes = [_P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P]
     L.cbev_reset.restype = _I
     L.cbev_bank_frames.argtypes = [_P, _P, _I, _P, _P]
@@ -124,7 +126,8 @@ EXPORTED_SYMBOLS = ("cbev_abi_version", "cbev_params_size", "cbev_layout_of", "c
                     "cbev_expand_obs", "cbev_vector_obs", "cbev_set_fov_mask", "cbev_set_obs_size", "cbev_resize_obs", "cbev_profile", "cbev_profile_read",
                     "cbev_profile_raster", "cbev_error_flags", "cbev_set_episode_stats", "cbev_episode_slot",
                     "cbev_wall_clock_hz", "cbev_termination_count", "cbev_pack_frames", "cbev_unpack_frames",
-                    "cbev_expand_obs_typed", "cbev_unpack_obs", "cbev_set_split_step", "cbev_step_repeat")
+                    "cbev_expand_obs_typed", "cbev_unpack_obs", "cbev_set_split_step", "cbev_step_repeat",
+                    "cbev_step_masked")
 
 REPEAT_MAX = 64  # CBEV_REPEAT_MAX (include/cbev.h)
 

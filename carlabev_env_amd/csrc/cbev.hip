@@ -1544,6 +1544,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
   if (actors_frozen(term, n)) return;
   actors_body<false, 4>(K, recs, n);
 }
+// cbev_step_masked: the caller's mask beside that gate. A wave whose env is
+// inactive exits after one byte load; substeps 2.. (term != nullptr) also read
+// the env's term byte of this agent step.
+__device__ __forceinline__ bool actors_masked_out(const uint8_t* __restrict__ active,
+                                                  const uint8_t* __restrict__ term, int n) {
+  const int e = xcd_env4_of_wg(blockIdx.x, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n);
+  if (e >= n) return false;
+  if (active[e] == 0) return true;
+  return term != nullptr && term[e] != 0;
+}
+template <bool WIDE, int MINAW>
+__global__ __launch_bounds__(256) void k_actors_mask(KArgs K, uint8_t* __restrict__ recs, int n,
+                                                     const uint8_t* __restrict__ active,
+                                                     const uint8_t* __restrict__ term) {
+  if (actors_masked_out(active, term, n)) return;
+  actors_body<WIDE, MINAW>(K, recs, n);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_actors_g4_mask(
+    KArgs K, uint8_t* __restrict__ recs, int n, const uint8_t* __restrict__ active,
+    const uint8_t* __restrict__ term) {
+  if (actors_masked_out(active, term, n)) return;
+  actors_body<false, 4>(K, recs, n);
+}
 
 
 // ====================================================== k_raster: the tile raster
@@ -3002,10 +3025,13 @@ __device__ __forceinline__ void ego_coll_prologue(const KArgs& K, const DRec& r,
 // workgroup and gets its registers in C; returns false when the workgroup has no
 // env. Otherwise (k_ego_head) the records are written back here: HD, HI, the
 // vis group, and a reset env's remaining pieces.
-template <bool WHOLE>
+// GATE == EgoGate::Mask (k_ego_mask): the action of an env whose bit of `frozen`
+// is set is not decoded (a zero action instead), so it raises no error flag.
+enum class EgoGate { None, Term, Mask };
+template <bool WHOLE, EgoGate GATE = EgoGate::None>
 __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ recs, int n, int ne, int st_rb,
                                           int st_n0, int st_n, int st_raw_x, const KArgs& K,
-                                          const void* __restrict__ actions, EgoCarry& C) {
+                                          const void* __restrict__ actions, EgoCarry& C, uint64_t frozen = 0ull) {
   CBEV_STAMP(0, 0);
   const int e0 = staged_env0(blockIdx.x, ne, n);
   const int ne_eff = min(ne, n - e0);
@@ -3111,7 +3137,11 @@ __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ re
   // the yaw (wave 2) beside tan(clip(delta)) (wave 3), into LDS for S3
   if (wave >= 2 && lane < ne_eff) {
     float ag, asa, ab;
-    d_decode_action(K, actions, e0 + lane, &ag, &asa, &ab);
+    if (GATE == EgoGate::Mask && ((frozen >> lane) & 1ull)) {
+      ag = asa = ab = 0.0f;
+    } else {
+      d_decode_action(K, actions, e0 + lane, &ag, &asa, &ab);
+    }
     const double* ghd = (const double*)(src(lane) + K.L.hd);
     if (wave == 2) {
       pre[lane].g = ag;
@@ -3308,12 +3338,18 @@ __device__ __forceinline__ void ego_tail_out(const uint8_t* lds, uint8_t* __rest
 // terminal substep left them and none of its record is written back; what the
 // front and S5 computed for it stays in LDS. A live env's reward is added to
 // the agent step's sum, its other outputs are overwritten.
-template <bool WHOLE, bool GATED = false>
+// GATE == Mask (k_ego_mask, cbev_step_masked): the frozen envs come from the
+// caller (`frozen_in`: inactive, and from substep 2 on also terminated). FIRST
+// (substep 1): a live env's reward is overwritten as in the plain step, and a
+// frozen env's thread stores reward 0 and nothing else.
+template <bool WHOLE, EgoGate GATE = EgoGate::None, bool FIRST = false>
 __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ recs, int n, int ne, int st_rb,
                                          int st_n0, int st_n, int st_raw_x, const KArgs& K,
                                          double* __restrict__ reward_out, uint8_t* __restrict__ term_out,
                                          uint8_t* __restrict__ trunc_out, int32_t* __restrict__ cause_out,
-                                         float* __restrict__ info_out, EgoCarry& C) {
+                                         float* __restrict__ info_out, EgoCarry& C, uint64_t frozen_in = 0ull) {
+  constexpr bool GATED = GATE != EgoGate::None;
+  constexpr bool ACCUM = GATE == EgoGate::Term || (GATE == EgoGate::Mask && !FIRST);
   const int e0 = staged_env0(blockIdx.x, ne, n);
   const int ne_eff = min(ne, n - e0);
   if (ne_eff <= 0) return;
@@ -3366,7 +3402,8 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
   }
   const uint32_t tc0 = C.tc0;
   uint64_t frozen = 0ull;  // bit k: env e0 + k (each wave builds the workgroup's mask: ne <= 64)
-  if (GATED) frozen = __ballot(lane < ne_eff && term_out[e0 + (lane < ne_eff ? lane : 0)] != 0);
+  if (GATE == EgoGate::Term) frozen = __ballot(lane < ne_eff && term_out[e0 + (lane < ne_eff ? lane : 0)] != 0);
+  if (GATE == EgoGate::Mask) frozen = frozen_in;
   CBEV_STAMP(1, 0);
   // S5 (env k, element i) pairs: env k = tid / tpe, elements sub, sub + tpe, ...
   {
@@ -3513,10 +3550,12 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
     cp.spx = C.spx;  // tid < ne: wave 0, the lane that loaded them in S4
     cp.spy = C.spy;
     double rsum = 0.0;
-    if (GATED) rsum = reward_out[e0 + tid];  // r1 + .. + r(j-1)
+    if (ACCUM) rsum = reward_out[e0 + tid];  // r1 + .. + r(j-1)
     collide_env(K, r, e0 + tid, cp, reward_out, term_out, trunc_out, cause_out, info_out);
-    if (GATED) reward_out[e0 + tid] = rsum + r.hd[CBEV_HD_REWARD];
+    if (ACCUM) reward_out[e0 + tid] = rsum + r.hd[CBEV_HD_REWARD];
     if (r.hi[CBEV_HI_TERM]) K.tcount[e0 + tid] = tc0 + 1u;  // the next reset's bank row moves on
+  } else if (GATE == EgoGate::Mask && FIRST && tid < ne_eff) {
+    reward_out[e0 + tid] = 0.0;  // an inactive env's reward of this agent step
   }
   __syncthreads();
   CBEV_STAMP(1, 2);
@@ -3567,8 +3606,41 @@ __global__ __launch_bounds__(256) void k_ego_rep(uint8_t* __restrict__ recs, int
   extern __shared__ __align__(16) uint8_t lds[];
   EgoCarry C;
   if (!ego_front<true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C)) return;
-  ego_tail<true, true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out, trunc_out, cause_out,
-                       info_out, C);
+  ego_tail<true, EgoGate::Term>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out, trunc_out,
+                                cause_out, info_out, C);
+}
+
+// cbev_step_masked's ego kernel. Substep 1 (FIRST): env e is frozen when
+// active[e] == 0; substeps 2..: when active[e] == 0 or its term byte of this
+// agent step is set. Each wave builds the workgroup's mask from one ballot
+// (ne <= 64), so the tests on it are uniform. A workgroup whose envs are all
+// frozen stages nothing: substep 1 stores their zero rewards, workgroup 0 still
+// clears the next statistics slot's count, and it returns.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void k_ego_mask(uint8_t* __restrict__ recs, int n, int ne, int st_rb, int st_n0,
+                                                  int st_n, int st_raw_x, KArgs K, const void* __restrict__ actions,
+                                                  const uint8_t* __restrict__ active, double* __restrict__ reward_out,
+                                                  uint8_t* __restrict__ term_out, uint8_t* __restrict__ trunc_out,
+                                                  int32_t* __restrict__ cause_out, float* __restrict__ info_out) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  const int e0 = staged_env0(blockIdx.x, ne, n);
+  const int ne_eff = min(ne, n - e0);
+  if (ne_eff <= 0) return;
+  const int lane = threadIdx.x & 63;
+  const int el = e0 + (lane < ne_eff ? lane : 0);
+  bool fz = active[el] == 0;
+  if (!FIRST) fz = fz || term_out[el] != 0;
+  const uint64_t frozen = __ballot(lane < ne_eff && fz);
+  const uint64_t all = ne_eff >= 64 ? ~0ull : (1ull << ne_eff) - 1ull;
+  if (frozen == all) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && K.ep_count_next != nullptr) *K.ep_count_next = 0;
+    if (FIRST && (int)threadIdx.x < ne_eff) reward_out[e0 + threadIdx.x] = 0.0;
+    return;
+  }
+  EgoCarry C;
+  if (!ego_front<true, EgoGate::Mask>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C, frozen)) return;
+  ego_tail<true, EgoGate::Mask, FIRST>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out,
+                                       trunc_out, cause_out, info_out, C, frozen);
 }
 
 // The split step's first launch: the front alone. It reads the previous step's
@@ -3648,6 +3720,58 @@ void k_raster(RasterArgs A) {
   raster_tile<G, true, kRasterNT>(K, r, J, t, frames + e * SS, 1, 0, lds);
   if (row >= 0) raster_reset_frame<G>(K, row, e, t);
   CBEV_STAMP(2, 3);
+}
+
+// cbev_step_masked's raster: k_raster's raster role (no tail workgroups, no
+// folded reset: the call flushes it) behind the caller's mask. The workgroup of
+// an inactive env renders nothing: its frame is the caller's previous one
+// (re-rendering would not even reproduce a reset frame), so it copies its tile
+// of prev_frames to frames with 16-byte streamed stores, or nothing when both
+// are the same slot, and returns before the record and window loads. The env
+// index is uniform over the workgroup.
+struct RasterMaskArgs {
+  KArgs K;
+  uint8_t* recs;
+  int n;
+  uint8_t* frames;
+  const uint8_t* active;
+  const uint8_t* prev_frames;
+};
+template <int G>
+__global__ __launch_bounds__(kRasterNT)
+__attribute__((amdgpu_waves_per_eu(Tiles<G>::wgs_per_cu * kRasterNT / 256 > 8 ? 8 : Tiles<G>::wgs_per_cu * kRasterNT / 256)))
+void k_raster_mask(RasterMaskArgs A) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  using TG = Tiles<G>;
+  const KArgs& K = A.K;
+  uint8_t* __restrict__ const frames = A.frames;
+  const int n = A.n;
+  int e, t;
+  xcd_tile_of_wg((int)blockIdx.x, n, TG::T, &e, &t);
+  if (e >= n) return;
+  const int64_t SS = (int64_t)K.P.size * K.P.size;
+  if (A.active[e] == 0) {
+    const uint8_t* const prev = A.prev_frames;
+    if (prev == frames) return;
+    constexpr int CPR = TG::TC / 16, PPT = TG::TC * TG::TR / 16 / kRasterNT;
+    const int ox0 = (t % TG::NTX) * TG::TC, oy0 = (t / TG::NTX) * TG::TR;
+    uint4 fv[PPT];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+      const int p = threadIdx.x + kRasterNT * j, pr = p / CPR;
+      fv[j] = *(const uint4*)(prev + e * SS + (oy0 + pr) * K.P.size + ox0 + 16 * (p - pr * CPR));
+    }
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+      const int p = threadIdx.x + kRasterNT * j, pr = p / CPR;
+      store16_frame(frames + e * SS + (oy0 + pr) * K.P.size + ox0 + 16 * (p - pr * CPR),
+                    u32x4_nt{fv[j].x, fv[j].y, fv[j].z, fv[j].w});
+    }
+    return;
+  }
+  const DRec r = bind_rec(A.recs + (int64_t)e * K.L.record_bytes, K.L, K.C);
+  const RasterJob J = raster_job<false, G>(K, r);
+  raster_tile<G, true, kRasterNT>(K, r, J, t, frames + e * SS, 1, 0, lds);
 }
 
 
@@ -4312,6 +4436,14 @@ typedef void (*ActorsRepKernel)(KArgs, uint8_t*, int, const uint8_t*);
 static ActorsRepKernel actors_rep_kernel(const cbev_caps& C) {  // actors_kernel's choice, gated
   return C.actor_cap > 64 ? k_actors_rep<true, 1> : C.actor_cap > 32 ? k_actors_rep<false, 1> : k_actors_g4_rep;
 }
+typedef void (*ActorsMaskKernel)(KArgs, uint8_t*, int, const uint8_t*, const uint8_t*);
+static ActorsMaskKernel actors_mask_kernel(const cbev_caps& C) {  // actors_kernel's choice, behind the caller's mask
+  return C.actor_cap > 64 ? k_actors_mask<true, 1> : C.actor_cap > 32 ? k_actors_mask<false, 1> : k_actors_g4_mask;
+}
+static const void* raster_mask_kernel(int size) {
+  return size == 64 ? (const void*)k_raster_mask<1> : size == 128 ? (const void*)k_raster_mask<2>
+                                                                  : (const void*)k_raster_mask<4>;
+}
 static const void* raster_kernel(int size) {
   return size == 64 ? (const void*)k_raster<1> : size == 128 ? (const void*)k_raster<2> : (const void*)k_raster<4>;
 }
@@ -4336,6 +4468,17 @@ static void launch_raster(const cbev_ctx* c, const KArgs& K, void* records, int 
     case 64: hipLaunchKernelGGL(k_raster<1>, dim3(n * Tiles<1>::T), dim3(kRasterNT), lb, s, A); break;
     case 128: hipLaunchKernelGGL(k_raster<2>, dim3(T.ntail + n * Tiles<2>::T), dim3(kRasterNT), lb, s, A); break;
     default: hipLaunchKernelGGL(k_raster<4>, dim3(T.ntail + n * Tiles<4>::T), dim3(kRasterNT), lb, s, A); break;
+  }
+}
+// cbev_step_masked's observation: the same grid without tail workgroups
+static void launch_raster_mask(const cbev_ctx* c, const KArgs& K, void* records, int n, uint8_t* frames,
+                               const uint8_t* active, const uint8_t* prev_frames, hipStream_t s) {
+  const size_t lb = raster_lds_bytes(c->P);
+  const RasterMaskArgs A{K, (uint8_t*)records, n, frames, active, prev_frames};
+  switch (c->P.size) {
+    case 64: hipLaunchKernelGGL(k_raster_mask<1>, dim3(n * Tiles<1>::T), dim3(kRasterNT), lb, s, A); break;
+    case 128: hipLaunchKernelGGL(k_raster_mask<2>, dim3(n * Tiles<2>::T), dim3(kRasterNT), lb, s, A); break;
+    default: hipLaunchKernelGGL(k_raster_mask<4>, dim3(n * Tiles<4>::T), dim3(kRasterNT), lb, s, A); break;
   }
 }
 // Envs per workgroup of k_raster's tail role: the largest group size not above
@@ -4492,7 +4635,14 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)k_ego_rep, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
   if (e == hipSuccess)
+    e = hipFuncSetAttribute((const void*)k_ego_mask<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute((const void*)k_ego_mask<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
+  if (e == hipSuccess)
     e = hipFuncSetAttribute(raster_kernel(P.size), hipFuncAttributeMaxDynamicSharedMemorySize, (int)raster_lds_bytes(P));
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(raster_mask_kernel(P.size), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)raster_lds_bytes(P));
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reset_kernel(P.size), hipFuncAttributeMaxDynamicSharedMemorySize, (int)raster_lds_bytes(P));
   if (e == hipSuccess)
@@ -4503,7 +4653,8 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
                             (int)raster_lds_bytes(P));
   // the byte-image gathers address the LDS absolutely: the crop image must be the
   // first thing in the workgroup's LDS (no static segment before it)
-  for (const void* kf : {raster_kernel(P.size), reset_kernel(P.size), bank_frames_kernel(P.size)}) {
+  for (const void* kf :
+       {raster_kernel(P.size), raster_mask_kernel(P.size), reset_kernel(P.size), bank_frames_kernel(P.size)}) {
     hipFuncAttributes fa;
     if (e == hipSuccess) e = hipFuncGetAttributes(&fa, kf);
     if (e == hipSuccess && fa.sharedSizeBytes != 0) {
@@ -4822,6 +4973,70 @@ int cbev_step_repeat(cbev_ctx* c, void* records, int n, const void* actions, int
   }
   if (ev) HIP_TRY(hipEventRecord(ev[2], s));
   launch_raster(c, K, records, n, frames, s, TailArgs{});  // the raster alone
+  if (ev) HIP_TRY(hipEventRecord(ev[3], s));
+  HIP_TRY(hipGetLastError());
+  return CBEV_OK;
+}
+
+// The masked step: cbev_step_repeat's chain (the unsplit ego kernel, then the
+// raster alone) with every launch behind the caller's device mask. Substep 1
+// is gated by `active` alone, substeps 2.. by `active` and this agent step's
+// term bytes. An inactive env's record, outputs but the reward (0) and
+// statistics are untouched, and its frame is prev_frames' (k_raster_mask).
+// repeat == 1 runs the same chain: nothing forwards to cbev_step.
+int cbev_step_masked(cbev_ctx* c, void* records, int n, const void* actions, const uint8_t* active, int repeat,
+                     const uint8_t* prev_frames, uint8_t* frames, double* reward, uint8_t* term, uint8_t* trunc,
+                     int32_t* cause, float* info, void* stream) {
+  if (!c || !records || !actions || !frames || !reward || !term || !trunc || !cause)
+    return set_err(CBEV_EINVAL, "null argument");
+  if (!active) return set_err(CBEV_EINVAL, "null active mask");
+  if (!prev_frames) return set_err(CBEV_EINVAL, "null prev_frames");
+  if (repeat < 1 || repeat > CBEV_REPEAT_MAX)
+    return set_err(CBEV_EINVAL, "repeat %d outside [1, %d]", repeat, CBEV_REPEAT_MAX);
+  if ((((uintptr_t)prev_frames) | ((uintptr_t)frames)) & 15u)
+    return set_err(CBEV_EINVAL, "frames and prev_frames must be 16-byte aligned");
+  if (!c->map_dev) return set_err(CBEV_ESTATE, "cbev_set_map not called");
+  if (n <= 0) return CBEV_OK;
+  if (c->stats && n > c->ep_n) return set_err(CBEV_EINVAL, "n %d exceeds the %d envs of the episode stats", n, c->ep_n);
+  CBEV_FLUSH(c);  // a deferred reset is launched first, as cbev_step_repeat does
+  hipStream_t s = (hipStream_t)stream;
+  KArgs K = kargs(c);
+  c->last_term = term;
+  c->last_n = n;
+  if (n > c->seq_n) c->seq_n = n;
+  if (c->stats) {  // every substep's rows into this call's slot
+    const int slot = (int)(c->step_count % c->ep_ring), next = (slot + 1) % c->ep_ring;
+    K.ep_rows = c->ep_rows + (int64_t)slot * c->ep_n * CBEV_EP_COUNT;
+    K.ep_count = c->ep_counts + slot;
+    K.ep_count_next = c->ep_counts + next;
+    K.ep_cap = c->ep_n;
+    c->step_count += 1;
+  }
+  const int wg4 = (n + 3) / 4;
+  const dim3 ego_grid((n + c->ego_ne - 1) / c->ego_ne);
+  const EgoPack pk = ego_pack(c->L);
+  // events as in cbev_step_repeat: 0 before substep 1, 1 after its actors kernel,
+  // 2 after the last substep's ego kernel, 3 after the raster
+  hipEvent_t* ev = nullptr;
+  if (c->prof_on && c->prof_n < CBEV_PROF_MAX) ev = c->prof_ev + 4 * c->prof_n++;
+  if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+  if (c->C.actor_cap > 0)
+    hipLaunchKernelGGL(actors_mask_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n, active,
+                       (const uint8_t*)nullptr);
+  if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+  hipLaunchKernelGGL(k_ego_mask<true>, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n, c->ego_ne,
+                     (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, active, reward, term, trunc,
+                     cause, info);
+  for (int j = 2; j <= repeat; ++j) {
+    if (c->C.actor_cap > 0)
+      hipLaunchKernelGGL(actors_mask_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n, active,
+                         (const uint8_t*)term);
+    hipLaunchKernelGGL(k_ego_mask<false>, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n,
+                       c->ego_ne, (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, active, reward,
+                       term, trunc, cause, info);
+  }
+  if (ev) HIP_TRY(hipEventRecord(ev[2], s));
+  launch_raster_mask(c, K, records, n, frames, active, prev_frames, s);
   if (ev) HIP_TRY(hipEventRecord(ev[3], s));
   HIP_TRY(hipGetLastError());
   return CBEV_OK;

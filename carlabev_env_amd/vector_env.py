@@ -47,6 +47,27 @@ def _ptr(t: torch.Tensor | None):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def validate_active(active, num_envs: int, device):
+    """step(active=...): a bool or uint8 [num_envs] torch tensor on `device`, or
+    such a numpy array (uploaded by the step). Anything else is a ValueError,
+    raised before anything is launched. Returns the argument."""
+    if isinstance(active, torch.Tensor):
+        if active.device != torch.device(device):
+            raise ValueError(f"active is on {active.device}, the env on {device}")
+        dt, shape = active.dtype, tuple(active.shape)
+        ok = dt in (torch.bool, torch.uint8)
+    elif isinstance(active, np.ndarray):
+        dt, shape = active.dtype, tuple(active.shape)
+        ok = dt in (np.dtype(np.bool_), np.dtype(np.uint8))
+    else:
+        raise ValueError(f"active must be a torch tensor or a numpy array, got {type(active).__name__}")
+    if not ok:
+        raise ValueError(f"active has dtype {dt}: bool or uint8")
+    if shape != (int(num_envs),):
+        raise ValueError(f"active has shape {shape}, expected ({int(num_envs)},)")
+    return active
+
+
 # episode_info keys (Stats.get_episode_info, stats.py:127-148, + carlabev.py:180-181)
 # -> summary row column (include/cbev_layout.h CBEV_EP_FIELDS) and the Python
 # type of the reference's value, which sets the batched array's dtype the way
@@ -120,7 +141,8 @@ class CarlaBEVVectorEnv:
 
     def __init__(self, cfg, *, num_envs: int | None = None, device=None, caps: dict | None = None,
                  info_mode: str = "full", scene_generator=None, wrappers: bool = True, copy_obs: bool = True,
-                 defer_reset: bool = True, reset_pool=None, obs_dtype: str = "float32", action_repeat: int = 1):
+                 defer_reset: bool = True, reset_pool=None, obs_dtype: str = "float32", action_repeat: int = 1,
+                 freeze_done: bool = False):
         """wrappers=False gives the base `CarlaBEV` observation of every env, as a
         `SyncVectorEnv` of unwrapped `CarlaBEV(cfg)` would: (S, S, 3) uint8 RGB for the
         BEV modes, float32[7] for obs_mode="vector" (carlabev.py:233-244, spaces.py:54-61).
@@ -170,7 +192,22 @@ class CarlaBEVVectorEnv:
         step. The reward is the sum over the substeps an env ran; an env that
         terminates in a substep is frozen for the rest of the step, and its
         observation is the frame of its terminal substep. max_actions, the episode
-        length and the episode statistics count substeps."""
+        length and the episode statistics count substeps.
+
+        freeze_done: the evaluation mode, exactly one episode per env (a bool, default
+        False). Every step is a masked step (cbev_step_masked) with active = (term ==
+        0), computed on the device without a synchronisation: an env that has
+        terminated stands still, with its record, actors, statistics and counts
+        untouched, reward 0, and term / trunc / cause / info as its last step left
+        them, until a reset of that env (reset() with or without reset_mask,
+        reset_from_bank, reset_terminated, load_scenes) clears its term flag. Its
+        newest frame enters its frame stack once more per step (step(active=...)).
+        `infos` therefore hold each env's episode exactly once; all_done() and
+        done_mask() tell when to stop. reset_terminated() launches at once in this
+        mode (the masked step would launch a deferred reset first anyway)."""
+        if not isinstance(freeze_done, (bool, np.bool_)):
+            raise ValueError(f"freeze_done={freeze_done!r}: a bool")
+        self.freeze_done = bool(freeze_done)
         if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or not (
                 1 <= int(action_repeat) <= REPEAT_MAX):
             raise ValueError(f"action_repeat={action_repeat!r}: an int in [1, {REPEAT_MAX}]")
@@ -251,7 +288,9 @@ class CarlaBEVVectorEnv:
         self._p_ring, self._slot_bytes = self._ring.data_ptr(), N * h * w
         # the canonical reset folded into the next step (frames are rendered straight
         # into the ring only without a resize)
-        check(L.cbev_set_deferred_reset(ctx, 1 if (defer_reset and not self.resize) else 0), "cbev_set_deferred_reset")
+        check(L.cbev_set_deferred_reset(ctx, 1 if (defer_reset and not self.resize and not self.freeze_done) else 0),
+              "cbev_set_deferred_reset")
+        self._active = None  # bool[N], the masked step's mask (allocated by the first masked step)
         self._p_full = self.full.data_ptr() if self.full is not None else None
         self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         # spaces (envs/spaces.py:27-61 + wrapper spaces)
@@ -510,16 +549,39 @@ class CarlaBEVVectorEnv:
         if not self._stepped:
             raise RuntimeError("reset_terminated before any step()")
         if self.resize:
-            return self._reset_masked(self._term)
+            obs = self._reset_masked(self._term)
+            self._clear_term(None)
+            return obs
         # cbev_reset_terminated: recorded for the next step to fold in (cbev_set_deferred_reset)
         # or launched at once; its mask is the term buffer of the last step (this env's)
         check(lib().cbev_reset_terminated(self._ctx, self._p_step[0], self.num_envs, self._p_bank, self.bank.shape[0],
                                           self._p_bank_frames, self._p_ring, self.F, self._stream()),
               "cbev_reset_terminated")
         self._reset_pending = bool(lib().cbev_reset_pending(self._ctx))
+        self._clear_term(None)  # freeze_done: the reset was launched (never deferred), every set flag is reset
         if not self.auto_obs:
             return None
         return self._obs()
+
+    def _clear_term(self, mask: torch.Tensor | None):
+        """freeze_done: a reset clears the term flag of the envs it reset (mask: a
+        device tensor, None = all), after the reset's launch on the same stream."""
+        if not self.freeze_done:
+            return
+        if mask is None:
+            self._term.zero_()
+        else:
+            self._term.masked_fill_(mask.to(torch.bool), 0)
+
+    def done_mask(self) -> torch.Tensor:
+        """bool[N] on the device: the envs whose term flag is set (under freeze_done:
+        finished and standing still). No synchronisation."""
+        return self.term != 0
+
+    def all_done(self) -> bool:
+        """Has every env's term flag been set (synchronises)? The end of a
+        freeze_done evaluation."""
+        return bool(self.done_mask().all().item())
 
     def _reset_masked(self, mask: torch.Tensor):
         N, B = self.num_envs, self.bank.shape[0]
@@ -580,7 +642,9 @@ class CarlaBEVVectorEnv:
                 if self._all_mask is None:
                     self._all_mask = torch.ones(N, dtype=torch.uint8, device=self.device)
                 mask = self._all_mask
-            return self._reset_masked(mask)
+            obs = self._reset_masked(mask)
+            self._clear_term(mask)
+            return obs
         bank_idx = torch.as_tensor(bank_idx)  # the kernels read N int32 bank rows on this device
         if bank_idx.numel() != N:
             raise ValueError(f"bank_idx has {bank_idx.numel()} entries, expected {N}")
@@ -594,6 +658,7 @@ class CarlaBEVVectorEnv:
             check(lib().cbev_reset_frames(self._ctx, _ptr(self.records), N, _ptr(self.bank), B, _ptr(mask),
                                           _ptr(bank_idx), 0, _ptr(self.bank_frames), _ptr(self.ring), self.F,
                                           self._stream()), "cbev_reset_frames")
+        self._clear_term(mask)
         if not self.auto_obs:
             return None
         return self._obs()
@@ -612,6 +677,7 @@ class CarlaBEVVectorEnv:
                                1 if self.resize else self.F, self._stream()), "cbev_reset")
         if self.resize:
             self._resize_into_ring(None, all_slots=True)
+        self._clear_term(None)
 
     def _resize_into_ring(self, mask: torch.Tensor | None, all_slots: bool):
         """ResizeObservation + the mask/grayscale colour test of self.full into the ring:
@@ -690,6 +756,7 @@ class CarlaBEVVectorEnv:
             else:
                 check(lib().cbev_reset(self._ctx, _ptr(self.records), N, _ptr(staging), len(idx), _ptr(m), _ptr(bidx),
                                        0, _ptr(self.ring), self.F, self._stream()), "cbev_reset")
+            self._clear_term(m)
         obs = self._obs()
         infos = {}
         if len(idx):
@@ -720,17 +787,45 @@ class CarlaBEVVectorEnv:
             a = a.reshape(self.num_envs, 3).to(torch.float32).contiguous()
         return a
 
-    def step_async_only(self, actions):
-        """Enqueue one step; returns nothing and never synchronises (bench path)."""
+    def _active_mask(self, active):
+        """The masked step's mask in self._active (bool[N] on the device): the
+        caller's `active`, and-combined with term == 0 under freeze_done. Device
+        work only, no synchronisation."""
+        if self._active is None:
+            self._active = torch.empty(self.num_envs, dtype=torch.bool, device=self.device)
+        if active is not None and not isinstance(active, torch.Tensor):
+            active = torch.from_numpy(np.ascontiguousarray(active)).to(self.device)
+        if self.freeze_done:
+            torch.eq(self._term, 0, out=self._active)
+            if active is not None:
+                self._active.logical_and_(active)
+        else:
+            self._active.copy_(active)  # uint8 -> bool: != 0
+        return self._active.data_ptr()
+
+    def step_async_only(self, actions, active=None):
+        """Enqueue one step; returns nothing and never synchronises (bench path).
+        active: see step()."""
+        if active is not None:
+            validate_active(active, self.num_envs, self.device)
+        masked = active is not None or self.freeze_done
         a = self._actions_tensor(actions)
         if self.info_mode == "full":
             self._flush_pending()
             self._ep_step += 1
+        old = self.head
         self.head = (self.head + 1) % self.F
         frames = self._p_full if self.resize else self._p_ring + self.head * self._slot_bytes
         rec, rew, term, trunc, cause, info = self._p_step
         stream = self._stream()
-        if self.action_repeat == 1:
+        if masked:
+            # an inactive env keeps its frame: the old head slot's into the new one (the
+            # render-size frame in place with a resize, which then resizes it again)
+            prev = self._p_full if self.resize else self._p_ring + old * self._slot_bytes
+            check(lib().cbev_step_masked(self._ctx, rec, self.num_envs, a.data_ptr(), self._active_mask(active),
+                                         self.action_repeat, prev, frames, rew, term, trunc, cause, info, stream),
+                  "cbev_step_masked")
+        elif self.action_repeat == 1:
             check(lib().cbev_step(self._ctx, rec, self.num_envs, a.data_ptr(), frames, rew, term, trunc, cause, info,
                                   stream), "cbev_step")
         else:
@@ -755,8 +850,17 @@ class CarlaBEVVectorEnv:
         check(lib().cbev_error_flags(self._ctx, ctypes.byref(flags), 1 if clear else 0), "cbev_error_flags")
         return int(flags.value)
 
-    def step(self, actions):
-        self.step_async_only(actions)
+    def step(self, actions, active=None):
+        """One step of every env. active=None: the plain step. Otherwise a masked
+        step (cbev_step_masked): a bool or uint8 [N] tensor on the env's device, or a
+        numpy array (uploaded); an env whose entry is 0 stands still: record, actors,
+        statistics and counts untouched, reward 0, term / trunc / cause / info as
+        they were, no error flag from its action. Its newest frame is copied into
+        the new frame-stack slot, so it enters the env's stack once more: the
+        stacked observation of an inactive env shifts by one frame per step (by
+        design; per-env stack heads are not implemented). Under freeze_done the
+        mask is and-combined with term == 0."""
+        self.step_async_only(actions, active)
         obs = self._obs()
         rew = self.reward.clone()
         term = self.term.bool()

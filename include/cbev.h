@@ -86,6 +86,30 @@ int cbev_step(cbev_ctx* ctx, void* records, int n, const void* actions, uint8_t*
 int cbev_step_repeat(cbev_ctx* ctx, void* records, int n, const void* actions, int repeat, uint8_t* frames,
                      double* reward, uint8_t* term, uint8_t* trunc, int32_t* cause, float* info, void* stream);
 
+/* The masked step: cbev_step_repeat for the envs whose byte of `active`
+ * (uint8[n] on the device, read when the launches run) is not 0; the others
+ * stand still.
+ * An active env does what cbev_step_repeat(..., repeat, ...) does for it, bit
+ * for bit: substep 1 is never frozen by `term`, substeps 2..repeat are frozen
+ * from its terminal substep on.
+ * An inactive env: its record (RS_*, vis / vis_draw and the actors included)
+ * is untouched, its actors and lights do not move, it writes no episode row
+ * and changes no termination count or Stats accumulator, its action is not
+ * decoded (no error flag), reward[e] = 0.0, and term[e], trunc[e], cause[e]
+ * and its info row are left as they were. Its S*S bytes of `frames` become
+ * those of `prev_frames` (the caller's previous newest ring slot; both 16-byte
+ * aligned); prev_frames == frames leaves them untouched. Nothing is rendered
+ * for it.
+ * The checks are cbev_step_repeat's, plus non-null `active` and `prev_frames`;
+ * every refusal is CBEV_EINVAL before anything is launched. A deferred reset
+ * is launched first. One chain on `stream`, nothing allocated, capturable. The
+ * episode-statistics slot advances once per call; cbev_reset_terminated works
+ * after it; cbev_profile records the four events of a repeat call. repeat == 1
+ * runs the same (unsplit) chain: the call never forwards to cbev_step. */
+int cbev_step_masked(cbev_ctx* ctx, void* records, int n, const void* actions, const uint8_t* active, int repeat,
+                     const uint8_t* prev_frames, uint8_t* frames, double* reward, uint8_t* term, uint8_t* trunc,
+                     int32_t* cause, float* info, void* stream);
+
 /* Episode statistics on the device (Stats, src/deeprl/stats.py:87-148, and
  * CarlaBEV._check_termination, carlabev.py:177-185), so `infos["episode_info"]`
  * needs no per-step host work. The caller owns the buffers (device memory):
