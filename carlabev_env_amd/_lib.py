@@ -50,6 +50,8 @@ def lib():
     L.cbev_step_repeat.restype = _I
     L.cbev_step_masked.argtypes = [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]
     L.cbev_step_masked.restype = _I
+    L.cbev_step_heads.argtypes = [_P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]
+    L.cbev_step_heads.restype = _I
     L.cbev_reset.argtypes = [_P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P]
     L.cbev_reset.restype = _I
     L.cbev_bank_frames.argtypes = [_P, _P, _I, _P, _P]
@@ -78,6 +80,8 @@ def lib():
     L.cbev_expand_obs.restype = _I
     L.cbev_expand_obs_typed.argtypes = [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P]
     L.cbev_expand_obs_typed.restype = _I
+    L.cbev_expand_obs_heads.argtypes = [_P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P]
+    L.cbev_expand_obs_heads.restype = _I
     L.cbev_unpack_obs.argtypes = [_P, _P, _I, _I, _I, _P, _P]
     L.cbev_unpack_obs.restype = _I
     L.cbev_pack_frames.argtypes = [_P, _P, _I, _P, _P]
@@ -127,7 +131,7 @@ EXPORTED_SYMBOLS = ("cbev_abi_version", "cbev_params_size", "cbev_layout_of", "c
                     "cbev_profile_raster", "cbev_error_flags", "cbev_set_episode_stats", "cbev_episode_slot",
                     "cbev_wall_clock_hz", "cbev_termination_count", "cbev_pack_frames", "cbev_unpack_frames",
                     "cbev_expand_obs_typed", "cbev_unpack_obs", "cbev_set_split_step", "cbev_step_repeat",
-                    "cbev_step_masked")
+                    "cbev_step_masked", "cbev_step_heads", "cbev_expand_obs_heads")
 
 REPEAT_MAX = 64  # CBEV_REPEAT_MAX (include/cbev.h)
 

@@ -9,7 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "cbev.hip")
 OUT = os.path.join(HERE, "libcbev.so")
-DEPS = [SRC, os.path.join(HERE, "csrc", "cbev_device.h"), os.path.join(REPO, "include", "cbev.h"),
+DEPS = [SRC, os.path.join(HERE, "csrc", "cbev_device.h"), os.path.join(HERE, "csrc", "cbev_expand.inc"),
+        os.path.join(REPO, "include", "cbev.h"),
         os.path.join(REPO, "include", "cbev_layout.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -3616,20 +3616,34 @@ __global__ __launch_bounds__(256) void k_ego_rep(uint8_t* __restrict__ recs, int
 // (ne <= 64), so the tests on it are uniform. A workgroup whose envs are all
 // frozen stages nothing: substep 1 stores their zero rewards, workgroup 0 still
 // clears the next statistics slot's count, and it returns.
-template <bool FIRST>
-__global__ __launch_bounds__(256) void k_ego_mask(uint8_t* __restrict__ recs, int n, int ne, int st_rb, int st_n0,
-                                                  int st_n, int st_raw_x, KArgs K, const void* __restrict__ actions,
-                                                  const uint8_t* __restrict__ active, double* __restrict__ reward_out,
-                                                  uint8_t* __restrict__ term_out, uint8_t* __restrict__ trunc_out,
-                                                  int32_t* __restrict__ cause_out, float* __restrict__ info_out) {
-  extern __shared__ __align__(16) uint8_t lds[];
+// HEADS (k_ego_heads, cbev_step_heads' substep 1): thread e - e0 of the
+// workgroup (wave 0; it has just read active[e]) also advances an active env's
+// frame-stack head in place, heads[e] = (heads[e] % n_frames + 1) % n_frames.
+// One thread per env writes it, once per call, and the raster that reads it is
+// a later launch of the same stream.
+template <bool FIRST, bool HEADS>
+__device__ __forceinline__ void ego_mask_body(uint8_t* lds, uint8_t* __restrict__ recs, int n, int ne, int st_rb,
+                                              int st_n0, int st_n, int st_raw_x, const KArgs& K,
+                                              const void* __restrict__ actions, const uint8_t* __restrict__ active,
+                                              double* __restrict__ reward_out, uint8_t* __restrict__ term_out,
+                                              uint8_t* __restrict__ trunc_out, int32_t* __restrict__ cause_out,
+                                              float* __restrict__ info_out, uint8_t* __restrict__ heads,
+                                              int n_frames) {
   const int e0 = staged_env0(blockIdx.x, ne, n);
   const int ne_eff = min(ne, n - e0);
   if (ne_eff <= 0) return;
   const int lane = threadIdx.x & 63;
   const int el = e0 + (lane < ne_eff ? lane : 0);
+  uint32_t hb = 0;
+  if constexpr (HEADS) hb = heads[el];  // beside the mask byte: one memory latency, not two in a row
   bool fz = active[el] == 0;
   if (!FIRST) fz = fz || term_out[el] != 0;
+  if constexpr (HEADS) {
+    if ((int)threadIdx.x < ne_eff && !fz) {
+      const uint32_t F = (uint32_t)n_frames;
+      heads[el] = (uint8_t)((hb % F + 1u) % F);
+    }
+  }
   const uint64_t frozen = __ballot(lane < ne_eff && fz);
   const uint64_t all = ne_eff >= 64 ? ~0ull : (1ull << ne_eff) - 1ull;
   if (frozen == all) {
@@ -3641,6 +3655,26 @@ __global__ __launch_bounds__(256) void k_ego_mask(uint8_t* __restrict__ recs, in
   if (!ego_front<true, EgoGate::Mask>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C, frozen)) return;
   ego_tail<true, EgoGate::Mask, FIRST>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out,
                                        trunc_out, cause_out, info_out, C, frozen);
+}
+template <bool FIRST>
+__global__ __launch_bounds__(256) void k_ego_mask(uint8_t* __restrict__ recs, int n, int ne, int st_rb, int st_n0,
+                                                  int st_n, int st_raw_x, KArgs K, const void* __restrict__ actions,
+                                                  const uint8_t* __restrict__ active, double* __restrict__ reward_out,
+                                                  uint8_t* __restrict__ term_out, uint8_t* __restrict__ trunc_out,
+                                                  int32_t* __restrict__ cause_out, float* __restrict__ info_out) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  ego_mask_body<FIRST, false>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, active, reward_out, term_out,
+                              trunc_out, cause_out, info_out, nullptr, 0);
+}
+__global__ __launch_bounds__(256) void k_ego_heads(uint8_t* __restrict__ recs, int n, int ne, int st_rb, int st_n0,
+                                                   int st_n, int st_raw_x, KArgs K, const void* __restrict__ actions,
+                                                   const uint8_t* __restrict__ active, double* __restrict__ reward_out,
+                                                   uint8_t* __restrict__ term_out, uint8_t* __restrict__ trunc_out,
+                                                   int32_t* __restrict__ cause_out, float* __restrict__ info_out,
+                                                   uint8_t* __restrict__ heads, int n_frames) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  ego_mask_body<true, true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, active, reward_out, term_out,
+                            trunc_out, cause_out, info_out, heads, n_frames);
 }
 
 // The split step's first launch: the front alone. It reads the previous step's
@@ -3774,6 +3808,44 @@ void k_raster_mask(RasterMaskArgs A) {
   raster_tile<G, true, kRasterNT>(K, r, J, t, frames + e * SS, 1, 0, lds);
 }
 
+// cbev_step_heads' raster: k_raster_mask with a frame-stack head per env. The
+// workgroup of an inactive env returns after the one byte load: its head and
+// its ring slots stay as they are, nothing is copied. An active env's head was
+// advanced by k_ego_heads, an earlier launch of the stream; every tile of the
+// env reads the same byte and renders into ring[heads[e] % n_frames][e]. The
+// modulo keeps the destination inside the ring whatever the byte holds.
+struct RasterHeadsArgs {
+  KArgs K;
+  uint8_t* recs;
+  int n;
+  uint8_t* ring;  // uint8[n_frames][n][S][S]
+  const uint8_t* active;
+  const uint8_t* heads;
+  int n_frames;
+};
+template <int G>
+__global__ __launch_bounds__(kRasterNT)
+__attribute__((amdgpu_waves_per_eu(Tiles<G>::wgs_per_cu * kRasterNT / 256 > 8 ? 8 : Tiles<G>::wgs_per_cu * kRasterNT / 256)))
+void k_raster_heads(RasterHeadsArgs A) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  const KArgs& K = A.K;
+  const int n = A.n;
+  int e, t;
+  xcd_tile_of_wg((int)blockIdx.x, n, Tiles<G>::T, &e, &t);
+  if (e >= n) return;
+  // both bytes loaded before the test (one memory latency, not two in a row); e is uniform
+  // over the workgroup, so the slot, and with it the frame's address, stays scalar
+  const uint32_t act = A.active[e];
+  const uint32_t hb = __builtin_amdgcn_readfirstlane((uint32_t)A.heads[e]);
+  if (act == 0) return;
+  const int64_t SS = (int64_t)K.P.size * K.P.size;
+  const int64_t slot = (int64_t)(hb % (uint32_t)A.n_frames);
+  uint8_t* __restrict__ const frame = A.ring + (slot * n + e) * SS;
+  const DRec r = bind_rec(A.recs + (int64_t)e * K.L.record_bytes, K.L, K.C);
+  const RasterJob J = raster_job<false, G>(K, r);
+  raster_tile<G, true, kRasterNT>(K, r, J, t, frame, 1, 0, lds);
+}
+
 
 // ============================================================== reset / ring / expansion
 // The 16 per-palette-id words of an expansion (channel bitmask / gray value /
@@ -3848,64 +3920,7 @@ __device__ __forceinline__ void store_nt(T* d, const T* v) {
   }
 }
 
-template <int FUSE, typename T, int V>
-__global__ __launch_bounds__(256) void k_expand_semantic(const uint8_t* __restrict__ ring, int n, int F, int head, int C,
-                                                         int vidx, int SS, Lut16 lut, T* __restrict__ out) {
-  const int nv = SS / V;
-  const int Cout = FUSE == 0 ? F * C : (FUSE == 1 ? C + 2 : C);
-  const int64_t total = (int64_t)n * nv;
-  for (int64_t q = blockIdx.x * 256ll + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
-    const int64_t e = q / nv;
-    const int64_t p = (q - e * nv) * V;
-    T* o = out + e * Cout * (int64_t)SS + p;
-    T vals[V];
-    if (FUSE == 0) {
-      for (int f = 0; f < F; ++f) {  // oldest -> newest
-        const int slot = (head + 1 + f) % F;
-        uint32_t m[V];
-        load_masks<V>(ring + ((int64_t)slot * n + e) * SS + p, lut, m);
-        for (int c = 0; c < C; ++c) {
-#pragma unroll
-          for (int k = 0; k < V; ++k) vals[k] = (T)((m[k] >> c) & 1);
-          store_nt<T, V>(o + (int64_t)(f * C + c) * SS, vals);
-        }
-      }
-    } else {
-      uint32_t m0[V], m1[V], m2[V];  // newest, newest-1, newest-2
-      load_masks<V>(ring + ((int64_t)head * n + e) * SS + p, lut, m0);
-      load_masks<V>(ring + ((int64_t)((head - 1 + F) % F) * n + e) * SS + p, lut, m1);
-      load_masks<V>(ring + ((int64_t)((head - 2 + 2 * F) % F) * n + e) * SS + p, lut, m2);
-      int oc = 0;
-      for (int c = 0; c < C; ++c) {  // static channels of the newest frame
-        if (c == vidx) continue;
-#pragma unroll
-        for (int k = 0; k < V; ++k) vals[k] = (T)((m0[k] >> c) & 1);
-        store_nt<T, V>(o + (int64_t)(oc++) * SS, vals);
-      }
-      if (FUSE == 1) {
-#pragma unroll
-        for (int k = 0; k < V; ++k) vals[k] = (T)((m0[k] >> vidx) & 1);
-        store_nt<T, V>(o + (int64_t)oc * SS, vals);
-#pragma unroll
-        for (int k = 0; k < V; ++k) vals[k] = (T)((m1[k] >> vidx) & 1);
-        store_nt<T, V>(o + (int64_t)(oc + 1) * SS, vals);
-#pragma unroll
-        for (int k = 0; k < V; ++k) vals[k] = (T)((m2[k] >> vidx) & 1);
-        store_nt<T, V>(o + (int64_t)(oc + 2) * SS, vals);
-      } else {
-#pragma unroll
-        for (int k = 0; k < V; ++k) {  // float32 in the reference's order, clipped, then converted
-          float acc = 0.0f;
-          acc += 1.0f * (float)((m0[k] >> vidx) & 1);
-          acc += 0.5f * (float)((m1[k] >> vidx) & 1);
-          acc += 0.25f * (float)((m2[k] >> vidx) & 1);
-          vals[k] = (T)fminf(fmaxf(acc, 0.0f), 1.0f);
-        }
-        store_nt<T, V>(o + (int64_t)oc * SS, vals);
-      }
-    }
-  }
-}
+// (k_expand_semantic: cbev_expand.inc, included below)
 
 // Bit-packed planes (FUSE 0 / 1): uint8[n][Cout][PB], PB = ceil(h*w / 8); pixel
 // p of a plane is bit p & 7 of byte p >> 3 (numpy.packbits, bitorder="little"),
@@ -3953,53 +3968,7 @@ __device__ __forceinline__ void store_bits(uint8_t* d, uint32_t w) {
     __builtin_nontemporal_store((uint8_t)w, d);
 }
 
-template <int FUSE, int V>
-__global__ __launch_bounds__(256) void k_expand_semantic_bits(const uint8_t* __restrict__ ring, int n, int F, int head,
-                                                              int C, int vidx, int SS, Lut16 lut,
-                                                              uint8_t* __restrict__ out) {
-  __shared__ uint32_t idset[16];
-  if (threadIdx.x < 16) {
-    uint32_t t = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t |= ((lut.v[i] >> threadIdx.x) & 1u) << i;
-    idset[threadIdx.x] = t;
-  }
-  __syncthreads();
-  const int PB = (SS + 7) >> 3;
-  const int nv = (SS + V - 1) / V;
-  const int Cout = FUSE == 0 ? F * C : C + 2;
-  const int64_t total = (int64_t)n * nv;
-  for (int64_t q = blockIdx.x * 256ll + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
-    const int64_t e = q / nv;
-    const int j = (int)(q - e * nv);
-    const int p = j * V, left = SS - p;
-    const uint32_t valid = left >= V ? 0xffffffffu : (1u << left) - 1u;
-    uint8_t* o = out + e * Cout * (int64_t)PB + j * (V / 8);
-    uint32_t id[V];
-    if (FUSE == 0) {
-      for (int f = 0; f < F; ++f) {  // oldest -> newest
-        const int slot = (head + 1 + f) % F;
-        load_ids_b<V>(ring + ((int64_t)slot * n + e) * SS + p, left, id);
-        for (int c = 0; c < C; ++c) store_bits<V>(o + (int64_t)(f * C + c) * PB, plane_bits<V>(id, idset[c], valid));
-      }
-    } else {
-      const uint32_t vset = idset[vidx];
-      load_ids_b<V>(ring + ((int64_t)((head - 1 + F) % F) * n + e) * SS + p, left, id);
-      const uint32_t v1 = plane_bits<V>(id, vset, valid);
-      load_ids_b<V>(ring + ((int64_t)((head - 2 + 2 * F) % F) * n + e) * SS + p, left, id);
-      const uint32_t v2 = plane_bits<V>(id, vset, valid);
-      load_ids_b<V>(ring + ((int64_t)head * n + e) * SS + p, left, id);
-      int oc = 0;
-      for (int c = 0; c < C; ++c) {  // static channels of the newest frame
-        if (c == vidx) continue;
-        store_bits<V>(o + (int64_t)(oc++) * PB, plane_bits<V>(id, idset[c], valid));
-      }
-      store_bits<V>(o + (int64_t)oc * PB, plane_bits<V>(id, vset, valid));
-      store_bits<V>(o + (int64_t)(oc + 1) * PB, v1);
-      store_bits<V>(o + (int64_t)(oc + 2) * PB, v2);
-    }
-  }
-}
+// (k_expand_semantic_bits: cbev_expand.inc, included below)
 
 // The learner's side of the bit-packed planes: packed uint8[rows][ceil(P / 8)]
 // -> T[rows][P] (float32, float16 or uint8 0 / 1). WIDE (P a multiple of 8,
@@ -4044,38 +4013,38 @@ __global__ __launch_bounds__(256) void k_unpack_bits(const uint8_t* __restrict__
 
 // Grayscale + frame stack: out[e][f][p] (uint8), oldest first. RAW: the ring
 // already holds gray values (the resize path), copied as they are.
-template <bool RAW, int V>
-__global__ __launch_bounds__(256) void k_expand_gray(const uint8_t* __restrict__ ring, int n, int F, int head, int SS,
-                                                     Lut16 lut, uint8_t* __restrict__ out) {
-  const int nv = SS / V;
-  const int64_t total = (int64_t)n * F * nv;
-  for (int64_t q = blockIdx.x * 256ll + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
-    const int64_t pv = q % nv;
-    const int64_t ef = q / nv;
-    const int f = (int)(ef % F);
-    const int64_t e = ef / F;
-    const int slot = (head + 1 + f) % F;
-    const uint8_t* src = ring + ((int64_t)slot * n + e) * SS + pv * V;
-    uint8_t* dst = out + (e * F + f) * (int64_t)SS + pv * V;
-    if (V == 16) {
-      uint4 ids = *(const uint4*)src;
-      if (!RAW) {
-        uint32_t in[4] = {ids.x, ids.y, ids.z, ids.w}, o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          o[k] = 0;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) o[k] |= (lut.v[(in[k] >> (8 * j)) & 15] & 255u) << (8 * j);
-        }
-        ids = make_uint4(o[0], o[1], o[2], o[3]);
-      }
-      nt_u4 x = {ids.x, ids.y, ids.z, ids.w};
-      __builtin_nontemporal_store(x, (nt_u4*)dst);
-    } else {
-      dst[0] = RAW ? src[0] : (uint8_t)lut.v[src[0] & 15];
-    }
-  }
+// (k_expand_gray: cbev_expand.inc)
+
+// The three expansion kernels, with one head for all envs and with a head per env
+#define CBEV_EXPAND_KERNEL(name) name
+#define CBEV_HEAD_PARAM int head
+#define CBEV_HEAD_OF_ENV
+#define CBEV_SLOT(x) ((x) % F)
+#include "cbev_expand.inc"
+#undef CBEV_EXPAND_KERNEL
+#undef CBEV_HEAD_PARAM
+#undef CBEV_HEAD_OF_ENV
+#undef CBEV_SLOT
+// env e's head, in [0, F) whatever the byte holds (a byte >= F is a caller error:
+// unspecified frame order, never an address outside the ring)
+__device__ __forceinline__ int env_head(const uint8_t* __restrict__ heads, int64_t e, int F) {
+  int h = heads[e];
+  if (h >= F) h %= F;
+  return h;
 }
+__device__ __forceinline__ int wrap_slot(int x, int F) {  // x % F for 0 <= x < 3 F, without a division
+  if (x >= 2 * F) x -= 2 * F;
+  return x >= F ? x - F : x;
+}
+#define CBEV_EXPAND_KERNEL(name) name##_heads
+#define CBEV_HEAD_PARAM const uint8_t* __restrict__ heads
+#define CBEV_HEAD_OF_ENV const int head = env_head(heads, e, F);
+#define CBEV_SLOT(x) wrap_slot(x, F)
+#include "cbev_expand.inc"
+#undef CBEV_EXPAND_KERNEL
+#undef CBEV_HEAD_PARAM
+#undef CBEV_HEAD_OF_ENV
+#undef CBEV_SLOT
 
 // RGB of the newest frame: out[e][p][3]
 __global__ __launch_bounds__(256) void k_expand_rgb(const uint8_t* __restrict__ ring, int n, int head, int SS, Lut16 lut,
@@ -4481,6 +4450,17 @@ static void launch_raster_mask(const cbev_ctx* c, const KArgs& K, void* records,
     default: hipLaunchKernelGGL(k_raster_mask<4>, dim3(n * Tiles<4>::T), dim3(kRasterNT), lb, s, A); break;
   }
 }
+// cbev_step_heads' observation: that grid, each active env into its own ring slot
+static void launch_raster_heads(const cbev_ctx* c, const KArgs& K, void* records, int n, uint8_t* ring, int n_frames,
+                                const uint8_t* active, const uint8_t* heads, hipStream_t s) {
+  const size_t lb = raster_lds_bytes(c->P);
+  const RasterHeadsArgs A{K, (uint8_t*)records, n, ring, active, heads, n_frames};
+  switch (c->P.size) {
+    case 64: hipLaunchKernelGGL(k_raster_heads<1>, dim3(n * Tiles<1>::T), dim3(kRasterNT), lb, s, A); break;
+    case 128: hipLaunchKernelGGL(k_raster_heads<2>, dim3(n * Tiles<2>::T), dim3(kRasterNT), lb, s, A); break;
+    default: hipLaunchKernelGGL(k_raster_heads<4>, dim3(n * Tiles<4>::T), dim3(kRasterNT), lb, s, A); break;
+  }
+}
 // Envs per workgroup of k_raster's tail role: the largest group size not above
 // k_ego's (so CBEV_EGO_NE holds) whose record slots, collision scratch and
 // HeroPre fit the raster's LDS, whose size and residency stay what they are.
@@ -4529,10 +4509,11 @@ static uint32_t bank_stride(int n_bank) {
   return p % (uint32_t)n_bank;
 }
 
-// One launch of a semantic expansion kernel (k_expand_semantic, k_expand_semantic_bits); T from the kernel
-template <typename T>
-static void launch_sem(void (*k)(const uint8_t*, int, int, int, int, int, int, Lut16, T*), int grid, void* stream,
-                       const uint8_t* ring, int n, int F, int head, int C, int vidx, int SS, const Lut16& lut,
+// One launch of a semantic expansion kernel (k_expand_semantic, k_expand_semantic_bits, or their *_heads forms);
+// T and H (int head / const uint8_t* heads) from the kernel
+template <typename H, typename T>
+static void launch_sem(void (*k)(const uint8_t*, int, int, H, int, int, int, Lut16, T*), int grid, void* stream,
+                       const uint8_t* ring, int n, int F, H head, int C, int vidx, int SS, const Lut16& lut,
                        void* out) {
   hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, (hipStream_t)stream, ring, n, F, head, C, vidx, SS, lut, (T*)out);
 }
@@ -5042,6 +5023,68 @@ int cbev_step_masked(cbev_ctx* c, void* records, int n, const void* actions, con
   return CBEV_OK;
 }
 
+// The masked step with a frame-stack head per env: cbev_step_masked's chain,
+// with k_ego_heads as substep 1's ego kernel (it advances the heads of the
+// active envs in place, once per call) and k_raster_heads as the raster (an
+// active env into ring[heads[e]][e], an inactive env's workgroups return at
+// once: nothing is copied).
+int cbev_step_heads(cbev_ctx* c, void* records, int n, const void* actions, const uint8_t* active, int repeat,
+                    uint8_t* ring, int n_frames, uint8_t* heads, double* reward, uint8_t* term, uint8_t* trunc,
+                    int32_t* cause, float* info, void* stream) {
+  if (!c || !records || !actions || !reward || !term || !trunc || !cause) return set_err(CBEV_EINVAL, "null argument");
+  if (!active) return set_err(CBEV_EINVAL, "null active mask");
+  if (!ring) return set_err(CBEV_EINVAL, "null ring");
+  if (!heads) return set_err(CBEV_EINVAL, "null heads");
+  if (repeat < 1 || repeat > CBEV_REPEAT_MAX)
+    return set_err(CBEV_EINVAL, "repeat %d outside [1, %d]", repeat, CBEV_REPEAT_MAX);
+  if (n_frames < 1 || n_frames > 255) return set_err(CBEV_EINVAL, "n_frames %d outside [1, 255]", n_frames);
+  if (((uintptr_t)ring) & 15u) return set_err(CBEV_EINVAL, "ring must be 16-byte aligned");
+  if (!c->map_dev) return set_err(CBEV_ESTATE, "cbev_set_map not called");
+  if (n <= 0) return CBEV_OK;
+  if (c->stats && n > c->ep_n) return set_err(CBEV_EINVAL, "n %d exceeds the %d envs of the episode stats", n, c->ep_n);
+  CBEV_FLUSH(c);  // a deferred reset is launched first, as cbev_step_masked does
+  hipStream_t s = (hipStream_t)stream;
+  KArgs K = kargs(c);
+  c->last_term = term;
+  c->last_n = n;
+  if (n > c->seq_n) c->seq_n = n;
+  if (c->stats) {  // every substep's rows into this call's slot
+    const int slot = (int)(c->step_count % c->ep_ring), next = (slot + 1) % c->ep_ring;
+    K.ep_rows = c->ep_rows + (int64_t)slot * c->ep_n * CBEV_EP_COUNT;
+    K.ep_count = c->ep_counts + slot;
+    K.ep_count_next = c->ep_counts + next;
+    K.ep_cap = c->ep_n;
+    c->step_count += 1;
+  }
+  const int wg4 = (n + 3) / 4;
+  const dim3 ego_grid((n + c->ego_ne - 1) / c->ego_ne);
+  const EgoPack pk = ego_pack(c->L);
+  // events as in cbev_step_masked
+  hipEvent_t* ev = nullptr;
+  if (c->prof_on && c->prof_n < CBEV_PROF_MAX) ev = c->prof_ev + 4 * c->prof_n++;
+  if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+  if (c->C.actor_cap > 0)
+    hipLaunchKernelGGL(actors_mask_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n, active,
+                       (const uint8_t*)nullptr);
+  if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+  hipLaunchKernelGGL(k_ego_heads, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n, c->ego_ne,
+                     (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, active, reward, term, trunc,
+                     cause, info, heads, n_frames);
+  for (int j = 2; j <= repeat; ++j) {
+    if (c->C.actor_cap > 0)
+      hipLaunchKernelGGL(actors_mask_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n, active,
+                         (const uint8_t*)term);
+    hipLaunchKernelGGL(k_ego_mask<false>, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n,
+                       c->ego_ne, (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, active, reward,
+                       term, trunc, cause, info);
+  }
+  if (ev) HIP_TRY(hipEventRecord(ev[2], s));
+  launch_raster_heads(c, K, records, n, ring, n_frames, active, heads, s);
+  if (ev) HIP_TRY(hipEventRecord(ev[3], s));
+  HIP_TRY(hipGetLastError());
+  return CBEV_OK;
+}
+
 int cbev_reset(cbev_ctx* c, void* records, int n, const void* bank, int n_bank, const uint8_t* mask,
                const int32_t* bank_idx, int bank_offset, uint8_t* frames, int n_frames, void* stream) {
   if (!c || !records || !frames) return set_err(CBEV_EINVAL, "null argument");
@@ -5209,8 +5252,10 @@ int cbev_bank_stride(int n_bank) { return n_bank > 0 ? (int)bank_stride(n_bank) 
 
 // The semantic kinds (0, 3, 4) of cbev_expand_obs and cbev_expand_obs_typed, to
 // any wire type: the checks, the choice of kernel and the launch.
-static int expand_semantic(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int head, int kind, int n_channels,
-                           const uint32_t* lut_host, int out_dtype, void* out, void* stream) {
+// heads != nullptr: a head per env (cbev_expand_obs_heads; `head` is then unused, 0).
+static int expand_semantic(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int head, const uint8_t* heads,
+                           int kind, int n_channels, const uint32_t* lut_host, int out_dtype, void* out,
+                           void* stream) {
   CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
   if (!lut_host) return set_err(CBEV_EINVAL, "null lut");
   if (n_frames < 1 || head < 0 || head >= n_frames) return set_err(CBEV_EINVAL, "bad frame ring");
@@ -5237,23 +5282,35 @@ static int expand_semantic(cbev_ctx* c, const uint8_t* ring, int n, int n_frames
   const int V = wide ? VW : (bits ? 8 : 1);
   const int64_t threads = (int64_t)n * ((SS + V - 1) / V);
   const int grid = (int)std::min<int64_t>((threads + 255) / 256, 4096);
-  const auto launch = [&](auto wide_k, decltype(wide_k) narrow_k) {
-    launch_sem(wide ? wide_k : narrow_k, grid, stream, ring, n, n_frames, head, n_channels, vidx, SS, lut, out);
+  const auto launch = [&](auto wide_k, decltype(wide_k) narrow_k, auto wide_h, decltype(wide_h) narrow_h) {
+    if (heads)
+      launch_sem(wide ? wide_h : narrow_h, grid, stream, ring, n, n_frames, heads, n_channels, vidx, SS, lut, out);
+    else
+      launch_sem(wide ? wide_k : narrow_k, grid, stream, ring, n, n_frames, head, n_channels, vidx, SS, lut, out);
   };
+  // the global-head kernel and its per-env-head form, wide and narrow
+#define CBEV_SEM(FUSE_, T_, VW_)                                                                               \
+  launch(k_expand_semantic<FUSE_, T_, VW_>, k_expand_semantic<FUSE_, T_, 1>, k_expand_semantic_heads<FUSE_, T_, VW_>, \
+         k_expand_semantic_heads<FUSE_, T_, 1>)
+#define CBEV_SEM_BITS(FUSE_)                                                                                        \
+  launch(k_expand_semantic_bits<FUSE_, 32>, k_expand_semantic_bits<FUSE_, 8>, k_expand_semantic_bits_heads<FUSE_, 32>, \
+         k_expand_semantic_bits_heads<FUSE_, 8>)
   // 4 * FUSE + wire type; FUSE 2 to uint8 or bits is refused by cbev_expand_obs_typed
   switch (4 * (kind == 0 ? 0 : kind == 3 ? 1 : 2) + out_dtype) {
-    case 0 + CBEV_OBS_F32: launch(k_expand_semantic<0, float, 4>, k_expand_semantic<0, float, 1>); break;
-    case 0 + CBEV_OBS_F16: launch(k_expand_semantic<0, _Float16, 8>, k_expand_semantic<0, _Float16, 1>); break;
-    case 0 + CBEV_OBS_U8: launch(k_expand_semantic<0, uint8_t, 16>, k_expand_semantic<0, uint8_t, 1>); break;
-    case 0 + CBEV_OBS_BITS: launch(k_expand_semantic_bits<0, 32>, k_expand_semantic_bits<0, 8>); break;
-    case 4 + CBEV_OBS_F32: launch(k_expand_semantic<1, float, 4>, k_expand_semantic<1, float, 1>); break;
-    case 4 + CBEV_OBS_F16: launch(k_expand_semantic<1, _Float16, 8>, k_expand_semantic<1, _Float16, 1>); break;
-    case 4 + CBEV_OBS_U8: launch(k_expand_semantic<1, uint8_t, 16>, k_expand_semantic<1, uint8_t, 1>); break;
-    case 4 + CBEV_OBS_BITS: launch(k_expand_semantic_bits<1, 32>, k_expand_semantic_bits<1, 8>); break;
-    case 8 + CBEV_OBS_F32: launch(k_expand_semantic<2, float, 4>, k_expand_semantic<2, float, 1>); break;
-    case 8 + CBEV_OBS_F16: launch(k_expand_semantic<2, _Float16, 8>, k_expand_semantic<2, _Float16, 1>); break;
+    case 0 + CBEV_OBS_F32: CBEV_SEM(0, float, 4); break;
+    case 0 + CBEV_OBS_F16: CBEV_SEM(0, _Float16, 8); break;
+    case 0 + CBEV_OBS_U8: CBEV_SEM(0, uint8_t, 16); break;
+    case 0 + CBEV_OBS_BITS: CBEV_SEM_BITS(0); break;
+    case 4 + CBEV_OBS_F32: CBEV_SEM(1, float, 4); break;
+    case 4 + CBEV_OBS_F16: CBEV_SEM(1, _Float16, 8); break;
+    case 4 + CBEV_OBS_U8: CBEV_SEM(1, uint8_t, 16); break;
+    case 4 + CBEV_OBS_BITS: CBEV_SEM_BITS(1); break;
+    case 8 + CBEV_OBS_F32: CBEV_SEM(2, float, 4); break;
+    case 8 + CBEV_OBS_F16: CBEV_SEM(2, _Float16, 8); break;
     default: return set_err(CBEV_EINVAL, "no semantic expansion of kind %d to obs dtype %d", kind, out_dtype);
   }
+#undef CBEV_SEM
+#undef CBEV_SEM_BITS
   HIP_TRY(hipGetLastError());
   return CBEV_OK;
 }
@@ -5262,7 +5319,7 @@ int cbev_expand_obs(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int h
                     const uint32_t* lut_host, void* out, void* stream) {
   if (!c || !ring || !out) return set_err(CBEV_EINVAL, "null argument");
   if (kind == 0 || kind == 3 || kind == 4)
-    return expand_semantic(c, ring, n, n_frames, head, kind, n_channels, lut_host, CBEV_OBS_F32, out, stream);
+    return expand_semantic(c, ring, n, n_frames, head, nullptr, kind, n_channels, lut_host, CBEV_OBS_F32, out, stream);
   CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
   if (!lut_host && kind != 5) return set_err(CBEV_EINVAL, "null lut");
   if (n_frames < 1 || head < 0 || head >= n_frames) return set_err(CBEV_EINVAL, "bad frame ring");
@@ -5305,7 +5362,38 @@ int cbev_expand_obs_typed(cbev_ctx* c, const uint8_t* ring, int n, int n_frames,
     return set_err(CBEV_EINVAL, "the weighted vehicle history is fractional: obs dtype %d cannot hold it", out_dtype);
   if (!(kind == 0 || kind == 3 || kind == 4))  // refused there as an unknown kind
     return cbev_expand_obs(c, ring, n, n_frames, head, kind, n_channels, lut_host, out, stream);
-  return expand_semantic(c, ring, n, n_frames, head, kind, n_channels, lut_host, out_dtype, out, stream);
+  return expand_semantic(c, ring, n, n_frames, head, nullptr, kind, n_channels, lut_host, out_dtype, out, stream);
+}
+
+// cbev_expand_obs_typed with a head per env: the stacked kinds only (semantic
+// through expand_semantic, the gray stacks here as cbev_expand_obs launches them)
+int cbev_expand_obs_heads(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, const uint8_t* heads, int kind,
+                          int n_channels, const uint32_t* lut_host, int out_dtype, void* out, void* stream) {
+  if (!c || !ring || !heads || !out) return set_err(CBEV_EINVAL, "null argument");
+  if (out_dtype < CBEV_OBS_F32 || out_dtype > CBEV_OBS_BITS) return set_err(CBEV_EINVAL, "unknown obs dtype %d", out_dtype);
+  if (kind == 2) return set_err(CBEV_EINVAL, "expansion kind 2 (RGB of the newest frame) has no frame stack");
+  if (!(kind == 0 || kind == 1 || kind == 3 || kind == 4 || kind == 5))
+    return set_err(CBEV_EINVAL, "unknown expansion kind %d", kind);
+  if ((kind == 1 || kind == 5) && out_dtype != CBEV_OBS_U8)
+    return set_err(CBEV_EINVAL, "expansion kind %d is uint8: obs dtype %d does not apply", kind, out_dtype);
+  if (kind == 4 && (out_dtype == CBEV_OBS_U8 || out_dtype == CBEV_OBS_BITS))
+    return set_err(CBEV_EINVAL, "the weighted vehicle history is fractional: obs dtype %d cannot hold it", out_dtype);
+  if (n_frames > 255) return set_err(CBEV_EINVAL, "n_frames %d outside [1, 255]", n_frames);
+  if (kind == 0 || kind == 3 || kind == 4)
+    return expand_semantic(c, ring, n, n_frames, 0, heads, kind, n_channels, lut_host, out_dtype, out, stream);
+  CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
+  if (!lut_host && kind != 5) return set_err(CBEV_EINVAL, "null lut");
+  if (n_frames < 1) return set_err(CBEV_EINVAL, "bad frame ring");
+  Lut16 lut{};
+  if (lut_host) memcpy(lut.v, lut_host, sizeof lut.v);
+  if (n <= 0) return CBEV_OK;
+  const int SS = c->obs_h * c->obs_w;
+  const bool v16 = SS % 16 == 0;
+  hipLaunchKernelGGL(kind == 1 ? (v16 ? k_expand_gray_heads<false, 16> : k_expand_gray_heads<false, 1>)
+                               : (v16 ? k_expand_gray_heads<true, 16> : k_expand_gray_heads<true, 1>),
+                     dim3(4096), dim3(256), 0, (hipStream_t)stream, ring, n, n_frames, heads, SS, lut, (uint8_t*)out);
+  HIP_TRY(hipGetLastError());
+  return CBEV_OK;
 }
 
 int cbev_unpack_obs(cbev_ctx* c, const uint8_t* packed, int rows, int pixels, int out_dtype, void* out, void* stream) {

@@ -142,7 +142,7 @@ class CarlaBEVVectorEnv:
     def __init__(self, cfg, *, num_envs: int | None = None, device=None, caps: dict | None = None,
                  info_mode: str = "full", scene_generator=None, wrappers: bool = True, copy_obs: bool = True,
                  defer_reset: bool = True, reset_pool=None, obs_dtype: str = "float32", action_repeat: int = 1,
-                 freeze_done: bool = False):
+                 freeze_done: bool = False, stack_heads: str = "global"):
         """wrappers=False gives the base `CarlaBEV` observation of every env, as a
         `SyncVectorEnv` of unwrapped `CarlaBEV(cfg)` would: (S, S, 3) uint8 RGB for the
         BEV modes, float32[7] for obs_mode="vector" (carlabev.py:233-244, spaces.py:54-61).
@@ -201,13 +201,34 @@ class CarlaBEVVectorEnv:
         untouched, reward 0, and term / trunc / cause / info as its last step left
         them, until a reset of that env (reset() with or without reset_mask,
         reset_from_bank, reset_terminated, load_scenes) clears its term flag. Its
-        newest frame enters its frame stack once more per step (step(active=...)).
+        newest frame enters its frame stack once more per step (step(active=...))
+        unless stack_heads="per_env".
         `infos` therefore hold each env's episode exactly once; all_done() and
         done_mask() tell when to stop. reset_terminated() launches at once in this
-        mode (the masked step would launch a deferred reset first anyway)."""
+        mode (the masked step would launch a deferred reset first anyway).
+
+        stack_heads: where the frame stack's newest slot is. "global" (default): one
+        head for all envs, advanced by every step; an env a masked step leaves
+        inactive gets its newest frame copied into the new slot. "per_env": a head
+        per env (self.heads, uint8[N] on the device, zeros at first), advanced on the
+        device only when that env is stepped, so an inactive env's ring slots and its
+        stacked observation stay bit-identical until it is stepped again, and nothing
+        is rendered or copied for it. Every step then runs cbev_step_heads, the plain
+        one with a cached all-ones mask: it is the unsplit masked chain, not
+        cbev_step's split one ("Per-env frame-stack heads", has the
+        cost). Observations come from cbev_expand_obs_heads, the deferred reset is
+        off, and resets are unchanged (they fill every slot, so any head is right).
+        It needs the wrapped observation (a frame stack) at the render size: a
+        resize (obs_size != (size, size)) or wrappers=False raises ValueError;
+        sharding.FrameGather and cbev_pack_frames, which take one slot of a
+        global-head ring, are not supported on a per-env ring."""
         if not isinstance(freeze_done, (bool, np.bool_)):
             raise ValueError(f"freeze_done={freeze_done!r}: a bool")
         self.freeze_done = bool(freeze_done)
+        if not isinstance(stack_heads, str) or stack_heads not in ("global", "per_env"):
+            raise ValueError(f"stack_heads={stack_heads!r}: 'global' or 'per_env'")
+        self.stack_heads = stack_heads
+        self.per_env = stack_heads == "per_env"
         if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or not (
                 1 <= int(action_repeat) <= REPEAT_MAX):
             raise ValueError(f"action_repeat={action_repeat!r}: an int in [1, {REPEAT_MAX}]")
@@ -229,6 +250,11 @@ class CarlaBEVVectorEnv:
         if self.obs_dtype != "float32" and not (self.wrappers and self.cfg.masked):
             raise ValueError(f"obs_dtype={self.obs_dtype!r} applies to the wrapped obs_mode='bev_semantic' observation "
                              "only; this env's observation (gray stack, RGB or vector) takes obs_dtype='float32'")
+        if self.per_env and not self.wrappers:
+            raise ValueError("stack_heads='per_env' needs the wrapped observation: wrappers=False has no frame stack")
+        if self.per_env and tuple(int(v) for v in self.cfg.obs_size) != (int(self.cfg.size), int(self.cfg.size)):
+            raise ValueError(f"stack_heads='per_env' does not support a resize: obs_size={tuple(self.cfg.obs_size)} "
+                             f"!= ({self.cfg.size}, {self.cfg.size})")
         self.num_envs = int(num_envs if num_envs is not None else run.num_envs)
         self.info_mode = info_mode
         if device is None:
@@ -276,6 +302,8 @@ class CarlaBEVVectorEnv:
         # newest ring slot itself when there is no resize
         self.full = torch.zeros((N, S, S), dtype=torch.uint8, device=dev) if self.resize else None
         self.head = 0
+        # stack_heads="per_env": the slot of each env's newest frame (self.head is then unused)
+        self.heads = torch.zeros(N, dtype=torch.uint8, device=dev) if self.per_env else None
         self.reward = torch.zeros(N, dtype=torch.float64, device=dev)
         self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
         self.trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
@@ -288,7 +316,8 @@ class CarlaBEVVectorEnv:
         self._p_ring, self._slot_bytes = self._ring.data_ptr(), N * h * w
         # the canonical reset folded into the next step (frames are rendered straight
         # into the ring only without a resize)
-        check(L.cbev_set_deferred_reset(ctx, 1 if (defer_reset and not self.resize and not self.freeze_done) else 0),
+        check(L.cbev_set_deferred_reset(ctx, 1 if (defer_reset and not self.resize and not self.freeze_done and not self.per_env)
+                                          else 0),
               "cbev_set_deferred_reset")
         self._active = None  # bool[N], the masked step's mask (allocated by the first masked step)
         self._p_full = self.full.data_ptr() if self.full is not None else None
@@ -813,11 +842,26 @@ class CarlaBEVVectorEnv:
         if self.info_mode == "full":
             self._flush_pending()
             self._ep_step += 1
+        rec, rew, term, trunc, cause, info = self._p_step
+        stream = self._stream()
+        if self.per_env:
+            # every step is cbev_step_heads; the plain one with the cached all-ones mask
+            if masked:
+                m = self._active_mask(active)
+            else:
+                if self._all_mask is None:
+                    self._all_mask = torch.ones(self.num_envs, dtype=torch.uint8, device=self.device)
+                m = self._all_mask.data_ptr()
+            check(lib().cbev_step_heads(self._ctx, rec, self.num_envs, a.data_ptr(), m, self.action_repeat,
+                                        self._p_ring, self.F, self.heads.data_ptr(), rew, term, trunc, cause, info,
+                                        stream), "cbev_step_heads")
+            self._reset_pending = False
+            self._step_stream = stream.value or 0
+            self._stepped = True
+            return a
         old = self.head
         self.head = (self.head + 1) % self.F
         frames = self._p_full if self.resize else self._p_ring + self.head * self._slot_bytes
-        rec, rew, term, trunc, cause, info = self._p_step
-        stream = self._stream()
         if masked:
             # an inactive env keeps its frame: the old head slot's into the new one (the
             # render-size frame in place with a resize, which then resizes it again)
@@ -855,11 +899,12 @@ class CarlaBEVVectorEnv:
         step (cbev_step_masked): a bool or uint8 [N] tensor on the env's device, or a
         numpy array (uploaded); an env whose entry is 0 stands still: record, actors,
         statistics and counts untouched, reward 0, term / trunc / cause / info as
-        they were, no error flag from its action. Its newest frame is copied into
-        the new frame-stack slot, so it enters the env's stack once more: the
-        stacked observation of an inactive env shifts by one frame per step (by
-        design; per-env stack heads are not implemented). Under freeze_done the
-        mask is and-combined with term == 0."""
+        they were, no error flag from its action. Under stack_heads="global" its
+        newest frame is copied into the new frame-stack slot, so it enters the env's
+        stack once more: the stacked observation of an inactive env shifts by one
+        frame per step. Under stack_heads="per_env" (cbev_step_heads) its head and
+        ring slots are untouched: its observation is bit-identical to its last one.
+        Under freeze_done the mask is and-combined with term == 0."""
         self.step_async_only(actions, active)
         obs = self._obs()
         rew = self.reward.clone()
@@ -885,6 +930,12 @@ class CarlaBEVVectorEnv:
                 check(lib().cbev_expand_obs(self._ctx, _ptr(self.frames()[None]), self.num_envs, 1, 0, 2, 3,
                                             rgb_lut().ctypes.data_as(ctypes.c_void_p), _ptr(out),
                                             self._stream()), "cbev_expand_obs")
+            return out
+        if self.per_env:
+            check(lib().cbev_expand_obs_heads(self._ctx, _ptr(self.ring), self.num_envs, self.F, _ptr(self.heads),
+                                              self._obs_kind, self._obs_ch,
+                                              self._obs_lut.ctypes.data_as(ctypes.c_void_p), self._obs_code, _ptr(out),
+                                              self._stream()), "cbev_expand_obs_heads")
             return out
         check(lib().cbev_expand_obs_typed(self._ctx, _ptr(self.ring), self.num_envs, self.F, self.head, self._obs_kind,
                                           self._obs_ch, self._obs_lut.ctypes.data_as(ctypes.c_void_p), self._obs_code,
@@ -1002,6 +1053,8 @@ class CarlaBEVVectorEnv:
 
     def frames(self) -> torch.Tensor:
         """Newest render-size palette-id frames (N, S, S) uint8 (compact observation)."""
+        if self.per_env:  # each env's own newest slot
+            return self.ring[self.heads.long(), torch.arange(self.num_envs, device=self.device)]
         return self.full if self.resize else self.ring[self.head]  # self.ring applies a deferred reset
 
     def records_host(self) -> np.ndarray:

@@ -110,6 +110,36 @@ int cbev_step_masked(cbev_ctx* ctx, void* records, int n, const void* actions, c
                      const uint8_t* prev_frames, uint8_t* frames, double* reward, uint8_t* term, uint8_t* trunc,
                      int32_t* cause, float* info, void* stream);
 
+/* The masked step with a frame-stack head per env: cbev_step_masked for
+ * everything but the frames. `ring` is the whole frame ring,
+ * uint8[n_frames][n][S][S] (16-byte aligned), and heads (uint8[n] on the
+ * device) holds the ring slot of each env's newest frame.
+ * An active env: heads[e] = (heads[e] + 1) % n_frames, once per call whatever
+ * `repeat` is and whichever substep ends the env, and its frame is rendered
+ * into ring[heads[e]][e]. The head is advanced in place on the device by the
+ * first substep's ego kernel (one thread per env), an earlier launch of the
+ * stream than the raster, whose tiles only read it: a captured call replays
+ * correctly.
+ * An inactive env: heads[e] and all its ring slots are untouched, nothing is
+ * rendered or copied for it (there is no prev_frames), and the rest is
+ * cbev_step_masked's contract: record, actors, statistics and counts
+ * untouched, reward 0, term / trunc / cause / info kept, no error flag.
+ * The kernels reduce heads[e] modulo n_frames before they form an address, so
+ * a byte >= n_frames is a caller error with unspecified frame order for that
+ * env, never an access outside `ring`.
+ * cbev_reset, cbev_reset_masked, cbev_reset_terminated and cbev_reset_frames
+ * write a reset env's frame into all n_frames slots, so any head value is
+ * right after a reset: resets neither read nor write `heads`.
+ * Refusals (CBEV_EINVAL before anything is launched, the context as it was):
+ * cbev_step_masked's, null `ring` or `heads`, n_frames outside [1, 255], a
+ * ring that is not 16-byte aligned. A deferred reset is launched first. One
+ * chain on `stream`, nothing allocated, capturable; the episode-statistics
+ * slot advances once; cbev_reset_terminated works after it; cbev_profile
+ * records the four events of the masked call. */
+int cbev_step_heads(cbev_ctx* ctx, void* records, int n, const void* actions, const uint8_t* active, int repeat,
+                    uint8_t* ring, int n_frames, uint8_t* heads, double* reward, uint8_t* term, uint8_t* trunc,
+                    int32_t* cause, float* info, void* stream);
+
 /* Episode statistics on the device (Stats, src/deeprl/stats.py:87-148, and
  * CarlaBEV._check_termination, carlabev.py:177-185), so `infos["episode_info"]`
  * needs no per-step host work. The caller owns the buffers (device memory):
@@ -283,6 +313,16 @@ int cbev_expand_obs(cbev_ctx* ctx, const uint8_t* ring, int n, int n_frames, int
 #define CBEV_OBS_BITS 3
 int cbev_expand_obs_typed(cbev_ctx* ctx, const uint8_t* ring, int n, int n_frames, int head, int kind, int n_channels,
                           const uint32_t* channel_lut_host, int out_dtype, void* out, void* stream);
+/* cbev_expand_obs_typed of a ring with a head per env (cbev_step_heads): heads
+ * = uint8[n] on the device, heads[e] the slot of env e's newest frame, so its
+ * frame f (oldest first) is slot (heads[e] + 1 + f) % n_frames. The stacked
+ * kinds: 0, 3, 4 in the wire types above, 1 and 5 as CBEV_OBS_U8; kind 2 (the
+ * newest frame alone) is refused, and n_frames is at most 255. The other
+ * checks, the kernel choice, the channel order and the arithmetic are the
+ * typed call's; the kernels reduce heads[e] modulo n_frames. It allocates
+ * nothing (capturable) and uses the cbev_set_obs_size size. */
+int cbev_expand_obs_heads(cbev_ctx* ctx, const uint8_t* ring, int n, int n_frames, const uint8_t* heads, int kind,
+                          int n_channels, const uint32_t* channel_lut_host, int out_dtype, void* out, void* stream);
 int cbev_unpack_obs(cbev_ctx* ctx, const uint8_t* packed, int rows, int pixels, int out_dtype, void* out, void* stream);
 
 /* obs_mode "vector" (CarlaBEV.render, carlabev.py:237-244): out = float32[n][7],
