@@ -62,6 +62,8 @@ def lib():
     L.cbev_reset_masked.restype = _I
     L.cbev_reset_terminated.argtypes = [_P, _P, _I, _P, _I, _P, _P, _I, _P]
     L.cbev_reset_terminated.restype = _I
+    L.cbev_final_frames.argtypes = [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]
+    L.cbev_final_frames.restype = _I
     L.cbev_bank_cursor.argtypes = [_P, _P]
     L.cbev_bank_cursor.restype = _I
     L.cbev_reset_counts.argtypes = [_P, _P, _I]
@@ -131,7 +133,7 @@ EXPORTED_SYMBOLS = ("cbev_abi_version", "cbev_params_size", "cbev_layout_of", "c
                     "cbev_profile_raster", "cbev_error_flags", "cbev_set_episode_stats", "cbev_episode_slot",
                     "cbev_wall_clock_hz", "cbev_termination_count", "cbev_pack_frames", "cbev_unpack_frames",
                     "cbev_expand_obs_typed", "cbev_unpack_obs", "cbev_set_split_step", "cbev_step_repeat",
-                    "cbev_step_masked", "cbev_step_heads", "cbev_expand_obs_heads")
+                    "cbev_step_masked", "cbev_step_heads", "cbev_expand_obs_heads", "cbev_final_frames")
 
 REPEAT_MAX = 64  # CBEV_REPEAT_MAX (include/cbev.h)
 

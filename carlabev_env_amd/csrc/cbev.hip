@@ -2427,6 +2427,132 @@ __global__ __launch_bounds__(256) void k_reset_mask(int n, int n_bank, uint32_t 
 __host__ __forceinline__ int reset_mask_upt(int n) { return ((n + 15) / 16 + 255) / 256; }
 __host__ __forceinline__ size_t reset_mask_lds(int n) { return 1056 + 2 * 256 * (size_t)reset_mask_upt(n); }
 
+// k_reset_mask's ranking of a byte mask by one 256-thread workgroup, as
+// k_final_frames' own copy of the text (sharing it with k_reset_mask through
+// these functions kept that kernel's resource usage but changed 178 of its 1022
+// instructions): um[u] = the nonzero bits of 16-byte unit u, pre[t] = the
+// selected envs before thread t's units. Returns how many envs are selected.
+__device__ __forceinline__ int rank_mask(const uint8_t* __restrict__ mask, int n, int upt, int* pre, int* wsum,
+                                         uint16_t* um) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nu = (n + 15) >> 4;               // 16-byte units
+  const bool vec = ((uintptr_t)mask & 15u) == 0;
+  int cnt = 0;
+  for (int k = 0; k < upt; ++k) {
+    const int u = tid * upt + k;
+    uint32_t m = 0;
+    if (u < nu) {
+      if (vec && 16 * u + 16 <= n) {
+        m = nonzero_bytes16(*(const uint4*)(mask + 16 * (int64_t)u));
+      } else {
+        for (int b = 0; b < 16; ++b)
+          if (16 * u + b < n && mask[16 * (int64_t)u + b] != 0) m |= 1u << b;
+      }
+    }
+    um[u] = (uint16_t)m;
+    cnt += __popc(m);
+  }
+  // workgroup exclusive scan of cnt (wave inclusive scan by shuffles, then the wave totals)
+  int inc = cnt;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += o;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  int wpre = 0;
+  for (int w = 0; w < wave; ++w) wpre += wsum[w];
+  pre[tid] = wpre + inc - cnt;
+  const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  __syncthreads();
+  return total;
+}
+// the env of slot `slot` (< the total) of a mask ranked by rank_mask
+__device__ __forceinline__ int ranked_env(const int* pre, const uint16_t* um, int upt, int slot) {
+  // the thread whose slots hold `slot`: the last t with pre[t] <= slot
+  int lo = 0, hi = 255;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pre[mid] <= slot) lo = mid;
+    else hi = mid - 1;
+  }
+  int j = slot - pre[lo], u = lo * upt;
+  uint32_t m = um[u];
+  for (int pc = __popc(m); j >= pc; pc = __popc(m)) {
+    j -= pc;
+    m = um[++u];
+  }
+  return 16 * u + nth_set_bit(m, j);
+}
+// The frame stacks of the envs a mask selects, compacted in env order before a
+// reset overwrites their ring slots (cbev_final_frames): with e_0 < e_1 < ...
+// the selected envs, out[f][r] = ring[(H + 1 + f) % n_frames][e_r], H = the
+// env's head (heads[e] % n_frames, or `head`), so `out` holds the stacks oldest
+// first. Every workgroup ranks the whole mask itself (rank_mask, as
+// k_reset_mask does: k_reset_mask's LDS and bound on n), so slot r's env is the
+// same in all of them, no workgroup waits for another and nothing is counted
+// with atomics; the order is by env id. Pieces of (slot, frame, 16 KB chunk) are
+// dealt over the grid; workgroup 0 also writes out_env (each thread the envs of
+// its own units, then the -1 tail) and out_count. Rows r >= the count of `out`
+// are not written. WIDE: ring and out 16-byte aligned and SS % 16 == 0.
+// A template, first used at the end of this file, so that the compiler emits it
+// after every other kernel and those keep their places in the code object
+// (emitted among them it moved config 3's step by 0.6 us with no kernel's code
+// changed: DESIGN.md §3).
+#define FINAL_PU 4                      // 16-byte loads per thread in flight
+#define FINAL_PIECE (4096 * FINAL_PU)   // bytes per piece
+#define FINAL_WGS 512                   // k_final_frames' grid cap
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_final_frames(int n, int SS, int n_frames, int head, int upt,
+                                                      const uint8_t* __restrict__ mask,
+                                                      const uint8_t* __restrict__ heads,
+                                                      const uint8_t* __restrict__ ring, uint8_t* __restrict__ out,
+                                                      int32_t* __restrict__ out_env, int32_t* __restrict__ out_count) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  int* pre = (int*)lds;                      // as in k_reset_mask
+  int* wsum = pre + 257;
+  uint16_t* um = (uint16_t*)(lds + 1056);
+  const int tid = threadIdx.x;
+  const int total = rank_mask(mask, n, upt, pre, wsum, um);
+  if (blockIdx.x == 0) {
+    int r = pre[tid];
+    for (int k = 0; k < upt; ++k) {
+      const int u = tid * upt + k;
+      for (uint32_t m = um[u]; m; m &= m - 1) out_env[r++] = 16 * u + __builtin_ctz(m);
+    }
+    for (r = total + tid; r < n; r += 256) out_env[r] = -1;
+    if (tid == 0) out_count[0] = total;
+  }
+  const int cpf = (SS + FINAL_PIECE - 1) / FINAL_PIECE;  // chunks per frame
+  const int64_t pieces = (int64_t)total * n_frames * cpf;
+  for (int64_t p = blockIdx.x; p < pieces; p += gridDim.x) {
+    const int64_t sf = p / cpf;
+    const int c = (int)(p - sf * cpf), slot = (int)(sf / n_frames), f = (int)(sf - (int64_t)slot * n_frames);
+    const int e = ranked_env(pre, um, upt, slot);
+    const int h = heads ? heads[e] % n_frames : head;
+    const uint8_t* src = ring + ((int64_t)((h + 1 + f) % n_frames) * n + e) * SS;
+    uint8_t* dst = out + ((int64_t)f * n + slot) * SS;
+    const int o0 = c * FINAL_PIECE;
+    if (WIDE) {
+      uint4 v[FINAL_PU];
+#pragma unroll
+      for (int q = 0; q < FINAL_PU; ++q) {
+        const int o = o0 + 4096 * q + 16 * tid;
+        v[q] = *(const uint4*)(src + (o < SS ? o : 0));
+      }
+#pragma unroll
+      for (int q = 0; q < FINAL_PU; ++q) {
+        const int o = o0 + 4096 * q + 16 * tid;
+        if (o < SS) reset_store16(dst + o, v[q]);
+      }
+    } else {
+      const int o1 = o0 + FINAL_PIECE < SS ? o0 + FINAL_PIECE : SS;
+      for (int o = o0 + tid; o < o1; o += 256) dst[o] = src[o];
+    }
+  }
+}
+
 // ============================================================== collision / reward (k_ego S5-S6)
 // squared distance from (x, y) to raw-route segment i (carl_reward_fn.py:36-48)
 __device__ __forceinline__ double d_seg_dist2(const DRec& r, int i, double x, double y) {
@@ -4548,6 +4674,7 @@ const char* cbev_field_names(int group) {
   }
 }
 
+static const void* final_frames_kernel(bool wide);  // k_final_frames<wide>, at the end of this file
 int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cbev_ctx** out) {
   if (!params || !caps || !out) return set_err(CBEV_EINVAL, "null argument");
   const cbev_params& P = *params;
@@ -4629,6 +4756,10 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)k_reset_mask, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)reset_mask_lds(CBEV_RESET_MASK_MAX_N));
+  for (const bool wide : {false, true})
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(final_frames_kernel(wide), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)reset_mask_lds(CBEV_RESET_MASK_MAX_N));
   if (e == hipSuccess)
     e = hipFuncSetAttribute(bank_frames_kernel(P.size), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)raster_lds_bytes(P));
@@ -5604,4 +5735,34 @@ int cbev_debug_occupancy(int size, int lds_bytes) {
   return occ;
 }
 #endif
+
+// cbev_final_frames and final_frames_kernel stay the last functions of this file:
+// k_final_frames<> is first used here (see the kernel)
+int cbev_final_frames(cbev_ctx* c, const uint8_t* ring, int n, int n_frames, int head, const uint8_t* heads,
+                      const uint8_t* mask, uint8_t* out, int32_t* out_env, int32_t* out_count, void* stream) {
+  if (!c || !ring || !mask || !out || !out_env || !out_count) return set_err(CBEV_EINVAL, "null argument");
+  if (n_frames < 1 || n_frames > 255) return set_err(CBEV_EINVAL, "n_frames %d outside [1, 255]", n_frames);
+  if (!heads && (head < 0 || head >= n_frames))
+    return set_err(CBEV_EINVAL, "head %d outside [0, %d)", head, n_frames);
+  if (n > CBEV_RESET_MASK_MAX_N) return set_err(CBEV_EINVAL, "n %d exceeds %d", n, CBEV_RESET_MASK_MAX_N);
+  if (n <= 0) return CBEV_OK;
+  const int SS = c->obs_h * c->obs_w;
+  const uint64_t bytes = (uint64_t)n_frames * (uint64_t)n * (uint64_t)SS;
+  const uintptr_t r0 = (uintptr_t)ring, o0 = (uintptr_t)out;
+  if (r0 < o0 + bytes && o0 < r0 + bytes) return set_err(CBEV_EINVAL, "out overlaps the ring");
+  CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
+  const int cpf = (SS + FINAL_PIECE - 1) / FINAL_PIECE;
+  const int64_t pieces = (int64_t)n * n_frames * cpf;  // at most: every env selected
+  const int grid = pieces >= FINAL_WGS ? FINAL_WGS : (int)pieces;
+  const bool wide = ((r0 | o0) & 15) == 0 && SS % 16 == 0;
+  hipLaunchKernelGGL(wide ? k_final_frames<true> : k_final_frames<false>, dim3(grid), dim3(256), reset_mask_lds(n),
+                     (hipStream_t)stream, n, SS, n_frames, heads ? 0 : head, reset_mask_upt(n), mask, heads, ring, out,
+                     out_env, out_count);
+  HIP_TRY(hipGetLastError());
+  return CBEV_OK;
+}
 }  // extern "C"
+
+static const void* final_frames_kernel(bool wide) {
+  return wide ? (const void*)k_final_frames<true> : (const void*)k_final_frames<false>;
+}

@@ -142,7 +142,7 @@ class CarlaBEVVectorEnv:
     def __init__(self, cfg, *, num_envs: int | None = None, device=None, caps: dict | None = None,
                  info_mode: str = "full", scene_generator=None, wrappers: bool = True, copy_obs: bool = True,
                  defer_reset: bool = True, reset_pool=None, obs_dtype: str = "float32", action_repeat: int = 1,
-                 freeze_done: bool = False, stack_heads: str = "global"):
+                 freeze_done: bool = False, stack_heads: str = "global", autoreset: str = "disabled"):
         """wrappers=False gives the base `CarlaBEV` observation of every env, as a
         `SyncVectorEnv` of unwrapped `CarlaBEV(cfg)` would: (S, S, 3) uint8 RGB for the
         BEV modes, float32[7] for obs_mode="vector" (carlabev.py:233-244, spaces.py:54-61).
@@ -221,10 +221,34 @@ class CarlaBEVVectorEnv:
         It needs the wrapped observation (a frame stack) at the render size: a
         resize (obs_size != (size, size)) or wrappers=False raises ValueError;
         sharding.FrameGather and cbev_pack_frames, which take one slot of a
-        global-head ring, are not supported on a per-env ring."""
+        global-head ring, are not supported on a per-env ring.
+
+        autoreset: "disabled" (default) is the reference's env: the caller resets
+        (reset_terminated()). "same_step" is Gymnasium's SAME_STEP autoreset on the
+        device: step() runs the step, keeps the frame stacks of the envs whose term
+        flag it set (cbev_final_frames: palette ids, F * h * w bytes per ended env, in
+        env order), resets those envs from the attached bank exactly as
+        reset_terminated() would, and expands one observation, in which an env that
+        ended shows its reset observation. rew / term / trunc / infos are the
+        step's own (term stays True for the ended envs; their episode rows in infos
+        are the final info). final_obs() expands the kept stacks into the terminal
+        observations; final_env / final_count are the device tensors behind it.
+        With active=, only envs that are active in the step are reset and reported.
+        It needs an attached bank (a step without one raises), turns the deferred
+        reset off, refuses freeze_done=True (which never resets) and the bare
+        obs_mode="vector" observation (read from the records, which the reset
+        overwrites), and reset_terminated() raises in it. metadata["autoreset_mode"]
+        is "same_step" on the instance."""
+        if not isinstance(autoreset, str) or autoreset not in ("disabled", "same_step"):
+            raise ValueError(f"autoreset={autoreset!r}: 'disabled' or 'same_step'")
+        self.autoreset = autoreset
+        self.same_step = autoreset == "same_step"
         if not isinstance(freeze_done, (bool, np.bool_)):
             raise ValueError(f"freeze_done={freeze_done!r}: a bool")
         self.freeze_done = bool(freeze_done)
+        if self.same_step and self.freeze_done:
+            raise ValueError("autoreset='same_step' with freeze_done=True: one mode always resets an env that "
+                             "ended, the other never does")
         if not isinstance(stack_heads, str) or stack_heads not in ("global", "per_env"):
             raise ValueError(f"stack_heads={stack_heads!r}: 'global' or 'per_env'")
         self.stack_heads = stack_heads
@@ -250,6 +274,9 @@ class CarlaBEVVectorEnv:
         if self.obs_dtype != "float32" and not (self.wrappers and self.cfg.masked):
             raise ValueError(f"obs_dtype={self.obs_dtype!r} applies to the wrapped obs_mode='bev_semantic' observation "
                              "only; this env's observation (gray stack, RGB or vector) takes obs_dtype='float32'")
+        if self.same_step and not self.wrappers and self.cfg.obs_mode == "vector":
+            raise ValueError("autoreset='same_step' does not support the bare obs_mode='vector' observation: it is "
+                             "read from the records, which the reset overwrites")
         if self.per_env and not self.wrappers:
             raise ValueError("stack_heads='per_env' needs the wrapped observation: wrappers=False has no frame stack")
         if self.per_env and tuple(int(v) for v in self.cfg.obs_size) != (int(self.cfg.size), int(self.cfg.size)):
@@ -316,9 +343,16 @@ class CarlaBEVVectorEnv:
         self._p_ring, self._slot_bytes = self._ring.data_ptr(), N * h * w
         # the canonical reset folded into the next step (frames are rendered straight
         # into the ring only without a resize)
-        check(L.cbev_set_deferred_reset(ctx, 1 if (defer_reset and not self.resize and not self.freeze_done and not self.per_env)
-                                          else 0),
+        check(L.cbev_set_deferred_reset(ctx, 1 if (defer_reset and not self.resize and not self.freeze_done and not self.per_env
+                                                   and not self.same_step) else 0),
               "cbev_set_deferred_reset")
+        if self.same_step:
+            # the stash of cbev_final_frames: the ended envs' frame stacks (oldest first), their ids and count
+            self.metadata = dict(type(self).metadata, autoreset_mode="same_step")
+            self._final = torch.zeros_like(self._ring)
+            self._final_env = torch.full((N,), -1, dtype=torch.int32, device=dev)
+            self._final_count = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._final_mask = None  # uint8[N], term & active (allocated by the first step with active=)
         self._active = None  # bool[N], the masked step's mask (allocated by the first masked step)
         self._p_full = self.full.data_ptr() if self.full is not None else None
         self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
@@ -575,6 +609,9 @@ class CarlaBEVVectorEnv:
         (or none: folded into the next step), no host sync."""
         if self.bank is None:
             raise RuntimeError("no scene bank attached")
+        if self.same_step:
+            raise RuntimeError("reset_terminated() under autoreset='same_step': step() has already reset the envs "
+                               "that ended")
         if not self._stepped:
             raise RuntimeError("reset_terminated before any step()")
         if self.resize:
@@ -613,6 +650,12 @@ class CarlaBEVVectorEnv:
         return bool(self.done_mask().all().item())
 
     def _reset_masked(self, mask: torch.Tensor):
+        self._launch_reset_masked(mask)
+        if not self.auto_obs:
+            return None
+        return self._obs()
+
+    def _launch_reset_masked(self, mask: torch.Tensor):
         N, B = self.num_envs, self.bank.shape[0]
         rec = self._p_step[0]
         if self.resize:
@@ -622,9 +665,6 @@ class CarlaBEVVectorEnv:
         else:
             check(lib().cbev_reset_masked(self._ctx, rec, N, mask.data_ptr(), self._p_bank, B, self._p_bank_frames,
                                           self._p_ring, self.F, self._stream()), "cbev_reset_masked")
-        if not self.auto_obs:
-            return None
-        return self._obs()
 
     def bank_rows_used(self) -> int:
         """Bank rows the masked resets (reset_terminated, reset_from_bank without
@@ -837,6 +877,8 @@ class CarlaBEVVectorEnv:
         active: see step()."""
         if active is not None:
             validate_active(active, self.num_envs, self.device)
+        if self.same_step and self.bank is None:
+            raise RuntimeError("no scene bank attached")
         masked = active is not None or self.freeze_done
         a = self._actions_tensor(actions)
         if self.info_mode == "full":
@@ -858,6 +900,8 @@ class CarlaBEVVectorEnv:
             self._reset_pending = False
             self._step_stream = stream.value or 0
             self._stepped = True
+            if self.same_step:
+                self._autoreset(active is not None, stream)
             return a
         old = self.head
         self.head = (self.head + 1) % self.F
@@ -880,7 +924,67 @@ class CarlaBEVVectorEnv:
         self._stepped = True
         if self.resize:
             self._resize_into_ring(None, all_slots=False)
+        if self.same_step:
+            self._autoreset(active is not None, stream)
         return a
+
+    def _autoreset(self, masked: bool, stream):
+        """autoreset="same_step", after the step's launches on the same stream: keep
+        the frame stacks of the envs that ended (cbev_final_frames), then reset them
+        (the masked reset reset_terminated() runs). The mask is the step's term
+        buffer; with active= it is term & active (self._active holds the step's
+        mask), since an env that ended earlier and is inactive now still has its
+        term byte set."""
+        mask = self._term
+        if masked:
+            if self._final_mask is None:
+                self._final_mask = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
+            mask = torch.mul(self._term, self._active, out=self._final_mask)
+        check(lib().cbev_final_frames(self._ctx, self._p_ring, self.num_envs, self.F, self.head,
+                                      self.heads.data_ptr() if self.per_env else None, mask.data_ptr(),
+                                      self._final.data_ptr(), self._final_env.data_ptr(),
+                                      self._final_count.data_ptr(), stream), "cbev_final_frames")
+        self._launch_reset_masked(mask)
+
+    @property
+    def final_env(self) -> torch.Tensor:
+        """autoreset="same_step": int32[N] on the device, the ids of the envs the last
+        step reset in increasing order, then -1 (no synchronisation)."""
+        return self._final_env
+
+    @property
+    def final_count(self) -> torch.Tensor:
+        """autoreset="same_step": int32[1] on the device, how many envs the last step
+        reset (no synchronisation)."""
+        return self._final_count
+
+    def final_obs(self):
+        """autoreset="same_step": (rows, env_ids) of the envs the last step() reset.
+        rows: a new tensor [k, *single_observation_space.shape] in the env's wire type,
+        their terminal observations (what step() would have returned for them
+        without the reset); env_ids: int64[k] on the device, increasing. Waits for
+        the step's stream to read k; valid until the next step(). k == 0 gives
+        empty tensors."""
+        if not self.same_step:
+            raise RuntimeError("final_obs() needs autoreset='same_step'")
+        if not self._stepped:
+            raise RuntimeError("final_obs before any step()")
+        s = self._step_stream_obj()
+        (s if s is not None else torch.cuda.default_stream(self.device)).synchronize()
+        k = int(self._final_count.item())
+        rows = torch.empty((k, *self.obs_buf.shape[1:]), dtype=self.obs_buf.dtype, device=self.device)
+        env_ids = self._final_env[:k].to(torch.int64)
+        if k == 0:
+            return rows, env_ids
+        stash = self._final[:, :k].contiguous()  # a global-head ring of k envs, newest slot F - 1
+        if self.wrappers:
+            kind, ch, lut, code = self._obs_kind, self._obs_ch, self._obs_lut, self._obs_code
+        else:
+            kind, ch, lut, code = 2, 3, rgb_lut(), OBS_U8
+        check(lib().cbev_expand_obs_typed(self._ctx, _ptr(stash), k, self.F, self.F - 1, kind, ch,
+                                          lut.ctypes.data_as(ctypes.c_void_p), code, _ptr(rows), self._stream()),
+              "cbev_expand_obs_typed")
+        return rows, env_ids
 
     def errors(self, clear: bool = True) -> int:
         """CBEV_ERR_* bits the kernels raised since the last call (synchronises the

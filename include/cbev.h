@@ -224,6 +224,35 @@ int cbev_reset_masked(cbev_ctx* ctx, void* records, int n, const uint8_t* mask, 
  * of the last cbev_step on this context (n must be that step's n). */
 int cbev_reset_terminated(cbev_ctx* ctx, void* records, int n, const void* bank, int n_bank,
                           const uint8_t* bank_frames, uint8_t* frames, int n_frames, void* stream);
+/* The terminal observations of a same-step autoreset: the frame stacks of the
+ * envs `mask` selects, compacted in env order, to be called between the step
+ * and the reset that overwrites all their ring slots.
+ *   ring       uint8[n_frames][n][h][w], h x w = the cbev_set_obs_size size (the
+ *              render size by default), as the expansion calls take it
+ *   heads      uint8[n] on the device, the slot of each env's newest frame
+ *              (reduced modulo n_frames before any address is formed; `head` is
+ *              then ignored), or NULL: the global `head` in [0, n_frames)
+ *   mask       uint8[n] on the device, read when the launch runs; any nonzero
+ *              byte selects the env; any alignment
+ * With e_0 < e_1 < ... < e_(k-1) the selected envs and H_e the head of env e:
+ *   out        uint8[n_frames][n][h][w]: out[f][r] = ring[(H_(e_r) + 1 + f) % n_frames][e_r]
+ *              for r < k, the stacks oldest first, so `out` is itself a
+ *              global-head ring with head n_frames - 1 (cbev_expand_obs_typed with
+ *              n = k of its first k rows per slot); rows r >= k are not written
+ *   out_env    int32[n]: e_r for r < k, -1 for k <= r < n
+ *   out_count  int32[1]: k
+ * No atomics: every workgroup ranks the whole mask itself (as cbev_reset_masked's
+ * kernel does), so the order is by env id, no workgroup depends on another, and
+ * a captured call replays with the mask as it is at replay time. 16-byte
+ * aligned ring and out with h * w % 16 == 0 take 16-byte copies, anything else
+ * a byte copy. A deferred reset is launched first. One launch on `stream`,
+ * nothing allocated, capturable. CBEV_EINVAL before anything is launched: a
+ * null ctx, ring, mask, out, out_env or out_count; n_frames outside [1, 255];
+ * heads == NULL with head outside [0, n_frames); n > 2^20; out's bytes
+ * overlapping the ring's. n <= 0 returns CBEV_OK and does nothing. */
+int cbev_final_frames(cbev_ctx* ctx, const uint8_t* ring, int n, int n_frames, int head, const uint8_t* heads,
+                      const uint8_t* mask, uint8_t* out, int32_t* out_env, int32_t* out_count, void* stream);
+
 /* The sum of the per-env termination counts (synchronises the device): the
  * bank rows the canonical loop's resets have handed out since cbev_create. */
 int cbev_bank_cursor(cbev_ctx* ctx, int64_t* cursor);
