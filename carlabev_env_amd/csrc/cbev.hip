@@ -4535,57 +4535,27 @@ typedef void (*ActorsMaskKernel)(KArgs, uint8_t*, int, const uint8_t*, const uin
 static ActorsMaskKernel actors_mask_kernel(const cbev_caps& C) {  // actors_kernel's choice, behind the caller's mask
   return C.actor_cap > 64 ? k_actors_mask<true, 1> : C.actor_cap > 32 ? k_actors_mask<false, 1> : k_actors_g4_mask;
 }
-static const void* raster_mask_kernel(int size) {
-  return size == 64 ? (const void*)k_raster_mask<1> : size == 128 ? (const void*)k_raster_mask<2>
-                                                                  : (const void*)k_raster_mask<4>;
-}
-static const void* raster_kernel(int size) {
-  return size == 64 ? (const void*)k_raster<1> : size == 128 ? (const void*)k_raster<2> : (const void*)k_raster<4>;
-}
-static const void* bank_frames_kernel(int size) {
-  return size == 64 ? (const void*)k_bank_frames<1> : size == 128 ? (const void*)k_bank_frames<2>
-                                                                   : (const void*)k_bank_frames<4>;
-}
-static const void* reset_kernel(int size) {
-  return size == 64 ? (const void*)k_reset<1> : size == 128 ? (const void*)k_reset<2> : (const void*)k_reset<4>;
-}
+// The instance for this size of a kernel templated on G = size / 64. Kernel templates are emitted in the order
+// of their instances' first uses in this file, and moving kernels in the code object has cost time (DESIGN.md
+// section 3): the inner conditional is resolved first, so the order stays <1>, <2>, <4>, and the selectors below
+// stay in this order, k_raster_heads' ahead of the first use of k_ego_mask.
+#define CBEV_BY_SIZE(k_, size_) ((size_) == 64 || (size_) == 128 ? ((size_) == 64 ? k_<1> : k_<2>) : k_<4>)
+static const void* raster_mask_kernel(int size) { return (const void*)CBEV_BY_SIZE(k_raster_mask, size); }
+static const void* raster_kernel(int size) { return (const void*)CBEV_BY_SIZE(k_raster, size); }
+static const void* bank_frames_kernel(int size) { return (const void*)CBEV_BY_SIZE(k_bank_frames, size); }
+static const void* reset_kernel(int size) { return (const void*)CBEV_BY_SIZE(k_reset, size); }
+static auto raster_heads_kernel(int size) { return CBEV_BY_SIZE(k_raster_heads, size); }
 static size_t raster_lds_bytes(const cbev_params& P) {
   return P.size == 64 ? Tiles<1>::lds_bytes : P.size == 128 ? Tiles<2>::lds_bytes : Tiles<4>::lds_bytes;
 }
 static int raster_tiles(int size) { return size == 64 ? Tiles<1>::T : size == 128 ? Tiles<2>::T : Tiles<4>::T; }
-// One step's observation for n records: one workgroup per env.
-// T.ntail leading workgroups run k_ego's tail (the split step); T = {} for the raster alone.
-static void launch_raster(const cbev_ctx* c, const KArgs& K, void* records, int n, uint8_t* frames, hipStream_t s,
-                          const TailArgs& T) {
-  const size_t lb = raster_lds_bytes(c->P);
-  const RasterArgs A{K, (uint8_t*)records, n, frames, T};
-  switch (c->P.size) {
-    case 64: hipLaunchKernelGGL(k_raster<1>, dim3(n * Tiles<1>::T), dim3(kRasterNT), lb, s, A); break;
-    case 128: hipLaunchKernelGGL(k_raster<2>, dim3(T.ntail + n * Tiles<2>::T), dim3(kRasterNT), lb, s, A); break;
-    default: hipLaunchKernelGGL(k_raster<4>, dim3(T.ntail + n * Tiles<4>::T), dim3(kRasterNT), lb, s, A); break;
-  }
-}
-// cbev_step_masked's observation: the same grid without tail workgroups
-static void launch_raster_mask(const cbev_ctx* c, const KArgs& K, void* records, int n, uint8_t* frames,
-                               const uint8_t* active, const uint8_t* prev_frames, hipStream_t s) {
-  const size_t lb = raster_lds_bytes(c->P);
-  const RasterMaskArgs A{K, (uint8_t*)records, n, frames, active, prev_frames};
-  switch (c->P.size) {
-    case 64: hipLaunchKernelGGL(k_raster_mask<1>, dim3(n * Tiles<1>::T), dim3(kRasterNT), lb, s, A); break;
-    case 128: hipLaunchKernelGGL(k_raster_mask<2>, dim3(n * Tiles<2>::T), dim3(kRasterNT), lb, s, A); break;
-    default: hipLaunchKernelGGL(k_raster_mask<4>, dim3(n * Tiles<4>::T), dim3(kRasterNT), lb, s, A); break;
-  }
-}
-// cbev_step_heads' observation: that grid, each active env into its own ring slot
-static void launch_raster_heads(const cbev_ctx* c, const KArgs& K, void* records, int n, uint8_t* ring, int n_frames,
-                                const uint8_t* active, const uint8_t* heads, hipStream_t s) {
-  const size_t lb = raster_lds_bytes(c->P);
-  const RasterHeadsArgs A{K, (uint8_t*)records, n, ring, active, heads, n_frames};
-  switch (c->P.size) {
-    case 64: hipLaunchKernelGGL(k_raster_heads<1>, dim3(n * Tiles<1>::T), dim3(kRasterNT), lb, s, A); break;
-    case 128: hipLaunchKernelGGL(k_raster_heads<2>, dim3(n * Tiles<2>::T), dim3(kRasterNT), lb, s, A); break;
-    default: hipLaunchKernelGGL(k_raster_heads<4>, dim3(n * Tiles<4>::T), dim3(kRasterNT), lb, s, A); break;
-  }
+// One step's observation for n records, by k = CBEV_BY_SIZE(k_raster | k_raster_mask | k_raster_heads, size)
+// with its argument struct: raster_tiles workgroups per env, after ntail leading workgroups that run k_ego's
+// tail (k_raster in the split step; 0 for the raster alone, and never any at size 64: tail_ne_for)
+template <typename A>
+static void launch_raster(const cbev_ctx* c, void (*k)(A), int n, int ntail, hipStream_t s, const A& args) {
+  const int grid = (c->P.size == 64 ? 0 : ntail) + n * raster_tiles(c->P.size);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(kRasterNT), raster_lds_bytes(c->P), s, args);
 }
 // Envs per workgroup of k_raster's tail role: the largest group size not above
 // k_ego's (so CBEV_EGO_NE holds) whose record slots, collision scratch and
@@ -4642,6 +4612,64 @@ static void launch_sem(void (*k)(const uint8_t*, int, int, H, int, int, int, Lut
                        const uint8_t* ring, int n, int F, H head, int C, int vidx, int SS, const Lut16& lut,
                        void* out) {
   hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, (hipStream_t)stream, ring, n, F, head, C, vidx, SS, lut, (T*)out);
+}
+
+// ---- the step entries: cbev_step, cbev_step_repeat, cbev_step_masked, cbev_step_heads.
+// Each makes its own argument checks, then CBEV_STEP_CHECKS, then launches a
+// deferred reset (cbev_step may fold it instead), and only then step_begin: every
+// check comes before the first launch and before the context changes, so an
+// erroring call leaves the records, the episode slot and the profile as they were.
+#define CBEV_STEP_CHECKS(c, n)                                                                        \
+  do {                                                                                                \
+    if (!(c)->map_dev) return set_err(CBEV_ESTATE, "cbev_set_map not called");                        \
+    if ((n) <= 0) return CBEV_OK;                                                                     \
+    if ((c)->stats && (n) > (c)->ep_n)                                                                \
+      return set_err(CBEV_EINVAL, "n %d exceeds the %d envs of the episode stats", (n), (c)->ep_n); \
+  } while (0)
+
+// A step's launches: ev, the call's four profile events (null: not recorded), are 0 before substep 1, 1 after
+// its actors kernel, 2 after the last substep's ego kernel, 3 after the raster
+struct StepRun {
+  KArgs K;
+  hipStream_t s;
+  hipEvent_t* ev;
+};
+// The bookkeeping of one agent step, whatever its substeps: the reset mask of cbev_reset_terminated, the
+// step's episode slot (every substep's rows go to it), its profile events, and event 0.
+static int step_begin(cbev_ctx* c, int n, uint8_t* term, void* stream, StepRun* R) {
+  R->s = (hipStream_t)stream;
+  R->K = kargs(c);
+  c->last_term = term;
+  c->last_n = n;
+  if (n > c->seq_n) c->seq_n = n;
+  if (c->stats) {
+    const int slot = (int)(c->step_count % c->ep_ring), next = (slot + 1) % c->ep_ring;
+    R->K.ep_rows = c->ep_rows + (int64_t)slot * c->ep_n * CBEV_EP_COUNT;
+    R->K.ep_count = c->ep_counts + slot;
+    R->K.ep_count_next = c->ep_counts + next;
+    R->K.ep_cap = c->ep_n;
+    c->step_count += 1;
+  }
+  R->ev = c->prof_on && c->prof_n < CBEV_PROF_MAX ? c->prof_ev + 4 * c->prof_n++ : nullptr;
+  if (R->ev) HIP_TRY(hipEventRecord(R->ev[0], R->s));
+  return CBEV_OK;
+}
+static int step_end(const StepRun& R) {
+  if (R.ev) HIP_TRY(hipEventRecord(R.ev[3], R.s));
+  HIP_TRY(hipGetLastError());
+  return CBEV_OK;
+}
+// an actors kernel (none without actor slots) and an ego kernel over n records; `tail`: the kernel's last arguments
+template <typename Kernel, typename... Tail>
+static void launch_actors(const cbev_ctx* c, Kernel k, const StepRun& R, void* records, int n, Tail... tail) {
+  if (c->C.actor_cap == 0) return;
+  hipLaunchKernelGGL(k, dim3((n + 3) / 4), dim3(256), 0, R.s, R.K, (uint8_t*)records, n, tail...);
+}
+template <typename Kernel, typename... Tail>
+static void launch_ego(const cbev_ctx* c, Kernel k, const StepRun& R, void* records, int n, Tail... tail) {
+  const EgoPack pk = ego_pack(c->L);
+  hipLaunchKernelGGL(k, dim3((n + c->ego_ne - 1) / c->ego_ne), dim3(256), (size_t)c->ego_lb, R.s, (uint8_t*)records, n,
+                     c->ego_ne, (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, R.K, tail...);
 }
 
 
@@ -4869,7 +4897,8 @@ int cbev_profile_raster(cbev_ctx* c, void* records, int n, uint8_t* frames, int 
   HIP_TRY(hipEventCreate(&ev[0]));
   HIP_TRY(hipEventCreate(&ev[1]));
   HIP_TRY(hipEventRecord(ev[0], s));
-  for (int i = 0; i < reps; ++i) launch_raster(c, K, records, n, frames, s, TailArgs{});  // the raster alone
+  const RasterArgs A{K, (uint8_t*)records, n, frames, TailArgs{}};  // the raster alone
+  for (int i = 0; i < reps; ++i) launch_raster(c, CBEV_BY_SIZE(k_raster, c->P.size), n, 0, s, A);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ev[1], s));
   HIP_TRY(hipEventSynchronize(ev[1]));
@@ -4954,88 +4983,119 @@ int cbev_step(cbev_ctx* c, void* records, int n, const void* actions, uint8_t* f
               uint8_t* trunc, int32_t* cause, float* info, void* stream) {
   if (!c || !records || !actions || !frames || !reward || !term || !trunc || !cause)
     return set_err(CBEV_EINVAL, "null argument");
-  if (!c->map_dev) return set_err(CBEV_ESTATE, "cbev_set_map not called");
-  if (n <= 0) return CBEV_OK;
-  // every argument check before the first launch, so an error leaves the records untouched
-  if (c->stats && n > c->ep_n) return set_err(CBEV_EINVAL, "n %d exceeds the %d envs of the episode stats", n, c->ep_n);
-  hipStream_t s = (hipStream_t)stream;
-  KArgs K = kargs(c);
+  CBEV_STEP_CHECKS(c, n);
   // a deferred reset of these records whose ring holds `frames`: k_ego takes it
-  uint8_t* ego_term = term;
-  bool fold = false;
-  if (c->pend.on) {
-    const int64_t stride = (int64_t)n * c->P.size * c->P.size;
-    const int64_t off = frames - c->pend.frames;
-    fold = records == c->pend.records && n == c->pend.n && off >= 0 && off % stride == 0 &&
-           off / stride < c->pend.n_frames && fold_ok(c, n);
-    if (fold) {
-      K.rmask = c->pend.mask;
-      K.rbank = (const uint8_t*)c->pend.bank;
-      K.rbank_frames = c->pend.bank_frames;
-      K.rring = c->pend.frames;
-      K.rring_stride = stride;
-      K.rn_bank = c->pend.n_bank;
-      K.rn_frames = c->pend.n_frames;
-      K.rslot = (int)(off / stride);
-      K.rstride = bank_stride(c->pend.n_bank);
-      c->pend.on = 0;
-    } else {
-      CBEV_FLUSH(c);
-    }
+  const int64_t stride = (int64_t)n * c->P.size * c->P.size;
+  const int64_t off = c->pend.on ? frames - c->pend.frames : 0;
+  const bool fold = c->pend.on && records == c->pend.records && n == c->pend.n && off >= 0 && off % stride == 0 &&
+                    off / stride < c->pend.n_frames && fold_ok(c, n);
+  if (!fold) CBEV_FLUSH(c);
+  StepRun R;
+  const int rc = step_begin(c, n, term, stream, &R);
+  if (rc != CBEV_OK) return rc;
+  if (fold) {
+    R.K.rmask = c->pend.mask;
+    R.K.rbank = (const uint8_t*)c->pend.bank;
+    R.K.rbank_frames = c->pend.bank_frames;
+    R.K.rring = c->pend.frames;
+    R.K.rring_stride = stride;
+    R.K.rn_bank = c->pend.n_bank;
+    R.K.rn_frames = c->pend.n_frames;
+    R.K.rslot = (int)(off / stride);
+    R.K.rstride = bank_stride(c->pend.n_bank);
+    c->pend.on = 0;
   }
-  c->last_term = term;
-  c->last_n = n;
-  if (n > c->seq_n) c->seq_n = n;
-  const int wg4 = (n + 3) / 4;
-  hipEvent_t* ev = nullptr;
-  if (c->prof_on && c->prof_n < CBEV_PROF_MAX) ev = c->prof_ev + 4 * c->prof_n++;
-  if (ev) HIP_TRY(hipEventRecord(ev[0], s));
-  if (c->C.actor_cap > 0) hipLaunchKernelGGL(actors_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n);
-  if (ev) HIP_TRY(hipEventRecord(ev[1], s));
-  if (c->stats) {
-    const int slot = (int)(c->step_count % c->ep_ring), next = (slot + 1) % c->ep_ring;
-    K.ep_rows = c->ep_rows + (int64_t)slot * c->ep_n * CBEV_EP_COUNT;
-    K.ep_count = c->ep_counts + slot;
-    K.ep_count_next = c->ep_counts + next;
-    K.ep_cap = c->ep_n;
-    c->step_count += 1;
-  }
-  const EgoPack pk = ego_pack(c->L);
+  launch_actors(c, actors_kernel(c->C), R, records, n);
+  if (R.ev) HIP_TRY(hipEventRecord(R.ev[1], R.s));
   TailArgs T{};
   if (c->split) {
     // the front, then the raster's launch with the tail as its leading workgroups
     // (a multiple of 8 of them: the XCD placement of both roles stays)
-    hipLaunchKernelGGL(k_ego_head, dim3((n + c->ego_ne - 1) / c->ego_ne), dim3(256), (size_t)c->ego_lb, s,
-                       (uint8_t*)records, n, c->ego_ne, (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K,
-                       actions);
-    T.ntail = ((n + c->tail_ne - 1) / c->tail_ne + 7) & ~7;
-    T.ne = c->tail_ne;
-    T.rb = (int)c->L.record_bytes;
-    T.n0 = pk.n0;
-    T.np = pk.n;
-    T.raw_x = (int)c->L.raw_x;
-    T.reward = reward;
-    T.term = ego_term;
-    T.trunc = trunc;
-    T.cause = cause;
-    T.info = info;
+    launch_ego(c, k_ego_head, R, records, n, actions);
+    const EgoPack pk = ego_pack(c->L);
+    T = TailArgs{((n + c->tail_ne - 1) / c->tail_ne + 7) & ~7, c->tail_ne, (int)c->L.record_bytes, pk.n0, pk.n,
+                 (int)c->L.raw_x, reward, term, trunc, cause, info};
   } else {
-    hipLaunchKernelGGL(k_ego, dim3((n + c->ego_ne - 1) / c->ego_ne), dim3(256), (size_t)c->ego_lb, s,
-                       (uint8_t*)records, n, c->ego_ne, (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K,
-                       actions, reward, ego_term, trunc, cause, info);
+    launch_ego(c, k_ego, R, records, n, actions, reward, term, trunc, cause, info);
   }
-  if (ev) HIP_TRY(hipEventRecord(ev[2], s));
-  launch_raster(c, K, records, n, frames, s, T);
-  if (ev) HIP_TRY(hipEventRecord(ev[3], s));
-  HIP_TRY(hipGetLastError());
-  return CBEV_OK;
+  if (R.ev) HIP_TRY(hipEventRecord(R.ev[2], R.s));
+  launch_raster(c, CBEV_BY_SIZE(k_raster, c->P.size), n, T.ntail, R.s,
+                RasterArgs{R.K, (uint8_t*)records, n, frames, T});
+  return step_end(R);
 }
 
-// Action repeat: `repeat` simulation substeps with the same actions, one render.
-// Substep 1 is cbev_step's k_actors + unsplit k_ego; substeps 2.. are the gated
-// kernels (an env that terminated within this agent step is frozen from its
-// terminal substep on); then the raster alone, from the records as they stand.
-// One linear chain on `stream`, nothing allocated.
+// The unsplit chain of cbev_step_repeat (repeat >= 2), cbev_step_masked and
+// cbev_step_heads: `repeat` substeps with the same actions, then one render from
+// the records as they stand. One linear sequence on `stream`, nothing allocated.
+// The entries differ in the kernels alone:
+//   STEP_REPEAT  substep 1 is cbev_step's k_actors + unsplit k_ego; substeps 2.. are gated by this agent
+//                step's term bytes (an env is frozen from its terminal substep on); k_raster alone.
+//   STEP_MASKED  every launch behind the caller's device mask: substep 1 gated by `active`, substeps 2.. by
+//                `active` and the term bytes. An inactive env's record and outputs but the reward (0) and
+//                statistics are untouched; its frame is prev_frames' (k_raster_mask).
+//   STEP_HEADS   STEP_MASKED with a head per env: substep 1's k_ego_heads advances the active envs' heads in
+//                place, once per call; k_raster_heads renders an active env into ring[heads[e]][e].
+// A deferred reset is launched first, never folded: k_ego marks a folded reset's
+// bank row in RS_FAST, which the next substep's render set-up would overwrite
+// before the one raster at the end could copy the bank frame into the ring.
+enum StepKind { STEP_REPEAT, STEP_MASKED, STEP_HEADS };
+struct StepChain {
+  StepKind kind;
+  const uint8_t *active, *prev_frames;  // the mask (STEP_MASKED, STEP_HEADS); the kept frames (STEP_MASKED)
+  uint8_t* heads;                       // STEP_HEADS, with `frames` the ring of n_frames slots
+  int n_frames;
+};
+static int step_chain(cbev_ctx* c, const StepChain& S, void* records, int n, const void* actions, int repeat,
+                      uint8_t* frames, double* reward, uint8_t* term, uint8_t* trunc, int32_t* cause, float* info,
+                      void* stream) {
+  CBEV_STEP_CHECKS(c, n);
+  CBEV_FLUSH(c);
+  StepRun R;
+  const int rc = step_begin(c, n, term, stream, &R);
+  if (rc != CBEV_OK) return rc;
+  const bool plain = S.kind == STEP_REPEAT;
+  if (plain) launch_actors(c, actors_kernel(c->C), R, records, n);
+  else launch_actors(c, actors_mask_kernel(c->C), R, records, n, S.active, (const uint8_t*)nullptr);
+  if (R.ev) HIP_TRY(hipEventRecord(R.ev[1], R.s));
+  switch (S.kind) {
+    case STEP_REPEAT: launch_ego(c, k_ego, R, records, n, actions, reward, term, trunc, cause, info); break;
+    case STEP_MASKED:
+      launch_ego(c, k_ego_mask<true>, R, records, n, actions, S.active, reward, term, trunc, cause, info);
+      break;
+    case STEP_HEADS:
+      launch_ego(c, k_ego_heads, R, records, n, actions, S.active, reward, term, trunc, cause, info, S.heads,
+                 S.n_frames);
+      break;
+  }
+  for (int j = 2; j <= repeat; ++j) {
+    if (plain) {
+      launch_actors(c, actors_rep_kernel(c->C), R, records, n, (const uint8_t*)term);
+      launch_ego(c, k_ego_rep, R, records, n, actions, reward, term, trunc, cause, info);
+    } else {
+      launch_actors(c, actors_mask_kernel(c->C), R, records, n, S.active, (const uint8_t*)term);
+      launch_ego(c, k_ego_mask<false>, R, records, n, actions, S.active, reward, term, trunc, cause, info);
+    }
+  }
+  if (R.ev) HIP_TRY(hipEventRecord(R.ev[2], R.s));
+  uint8_t* const recs = (uint8_t*)records;
+  const int size = c->P.size;
+  switch (S.kind) {
+    case STEP_REPEAT:
+      launch_raster(c, CBEV_BY_SIZE(k_raster, size), n, 0, R.s, RasterArgs{R.K, recs, n, frames, TailArgs{}});
+      break;
+    case STEP_MASKED:
+      launch_raster(c, CBEV_BY_SIZE(k_raster_mask, size), n, 0, R.s,
+                    RasterMaskArgs{R.K, recs, n, frames, S.active, S.prev_frames});
+      break;
+    case STEP_HEADS:
+      launch_raster(c, raster_heads_kernel(size), n, 0, R.s,
+                    RasterHeadsArgs{R.K, recs, n, frames, S.active, S.heads, S.n_frames});
+      break;
+  }
+  return step_end(R);
+}
+
+// Action repeat; repeat == 1 is cbev_step (its split step and its folded reset included).
 int cbev_step_repeat(cbev_ctx* c, void* records, int n, const void* actions, int repeat, uint8_t* frames,
                      double* reward, uint8_t* term, uint8_t* trunc, int32_t* cause, float* info, void* stream) {
   if (!c || !records || !actions || !frames || !reward || !term || !trunc || !cause)
@@ -5043,59 +5103,11 @@ int cbev_step_repeat(cbev_ctx* c, void* records, int n, const void* actions, int
   if (repeat < 1 || repeat > CBEV_REPEAT_MAX)
     return set_err(CBEV_EINVAL, "repeat %d outside [1, %d]", repeat, CBEV_REPEAT_MAX);
   if (repeat == 1) return cbev_step(c, records, n, actions, frames, reward, term, trunc, cause, info, stream);
-  if (!c->map_dev) return set_err(CBEV_ESTATE, "cbev_set_map not called");
-  if (n <= 0) return CBEV_OK;
-  if (c->stats && n > c->ep_n) return set_err(CBEV_EINVAL, "n %d exceeds the %d envs of the episode stats", n, c->ep_n);
-  // a deferred reset is launched now: k_ego marks a folded reset's bank row in
-  // RS_FAST, which the next substep's render set-up would overwrite before the
-  // one raster at the end could copy the bank frame into the ring
-  CBEV_FLUSH(c);
-  hipStream_t s = (hipStream_t)stream;
-  KArgs K = kargs(c);
-  c->last_term = term;
-  c->last_n = n;
-  if (n > c->seq_n) c->seq_n = n;
-  if (c->stats) {  // every substep's rows into this agent step's slot
-    const int slot = (int)(c->step_count % c->ep_ring), next = (slot + 1) % c->ep_ring;
-    K.ep_rows = c->ep_rows + (int64_t)slot * c->ep_n * CBEV_EP_COUNT;
-    K.ep_count = c->ep_counts + slot;
-    K.ep_count_next = c->ep_counts + next;
-    K.ep_cap = c->ep_n;
-    c->step_count += 1;
-  }
-  const int wg4 = (n + 3) / 4;
-  const dim3 ego_grid((n + c->ego_ne - 1) / c->ego_ne);
-  const EgoPack pk = ego_pack(c->L);
-  // events: 0 before substep 1, 1 after its k_actors, 2 after the last substep's
-  // ego kernel, 3 after k_raster
-  hipEvent_t* ev = nullptr;
-  if (c->prof_on && c->prof_n < CBEV_PROF_MAX) ev = c->prof_ev + 4 * c->prof_n++;
-  if (ev) HIP_TRY(hipEventRecord(ev[0], s));
-  if (c->C.actor_cap > 0) hipLaunchKernelGGL(actors_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n);
-  if (ev) HIP_TRY(hipEventRecord(ev[1], s));
-  hipLaunchKernelGGL(k_ego, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n, c->ego_ne,
-                     (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, reward, term, trunc, cause, info);
-  for (int j = 2; j <= repeat; ++j) {
-    if (c->C.actor_cap > 0)
-      hipLaunchKernelGGL(actors_rep_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n,
-                         (const uint8_t*)term);
-    hipLaunchKernelGGL(k_ego_rep, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n, c->ego_ne,
-                       (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, reward, term, trunc, cause,
-                       info);
-  }
-  if (ev) HIP_TRY(hipEventRecord(ev[2], s));
-  launch_raster(c, K, records, n, frames, s, TailArgs{});  // the raster alone
-  if (ev) HIP_TRY(hipEventRecord(ev[3], s));
-  HIP_TRY(hipGetLastError());
-  return CBEV_OK;
+  return step_chain(c, StepChain{STEP_REPEAT, nullptr, nullptr, nullptr, 0}, records, n, actions, repeat, frames,
+                    reward, term, trunc, cause, info, stream);
 }
 
-// The masked step: cbev_step_repeat's chain (the unsplit ego kernel, then the
-// raster alone) with every launch behind the caller's device mask. Substep 1
-// is gated by `active` alone, substeps 2.. by `active` and this agent step's
-// term bytes. An inactive env's record, outputs but the reward (0) and
-// statistics are untouched, and its frame is prev_frames' (k_raster_mask).
-// repeat == 1 runs the same chain: nothing forwards to cbev_step.
+// The masked step. repeat == 1 runs the same chain: nothing forwards to cbev_step.
 int cbev_step_masked(cbev_ctx* c, void* records, int n, const void* actions, const uint8_t* active, int repeat,
                      const uint8_t* prev_frames, uint8_t* frames, double* reward, uint8_t* term, uint8_t* trunc,
                      int32_t* cause, float* info, void* stream) {
@@ -5107,58 +5119,11 @@ int cbev_step_masked(cbev_ctx* c, void* records, int n, const void* actions, con
     return set_err(CBEV_EINVAL, "repeat %d outside [1, %d]", repeat, CBEV_REPEAT_MAX);
   if ((((uintptr_t)prev_frames) | ((uintptr_t)frames)) & 15u)
     return set_err(CBEV_EINVAL, "frames and prev_frames must be 16-byte aligned");
-  if (!c->map_dev) return set_err(CBEV_ESTATE, "cbev_set_map not called");
-  if (n <= 0) return CBEV_OK;
-  if (c->stats && n > c->ep_n) return set_err(CBEV_EINVAL, "n %d exceeds the %d envs of the episode stats", n, c->ep_n);
-  CBEV_FLUSH(c);  // a deferred reset is launched first, as cbev_step_repeat does
-  hipStream_t s = (hipStream_t)stream;
-  KArgs K = kargs(c);
-  c->last_term = term;
-  c->last_n = n;
-  if (n > c->seq_n) c->seq_n = n;
-  if (c->stats) {  // every substep's rows into this call's slot
-    const int slot = (int)(c->step_count % c->ep_ring), next = (slot + 1) % c->ep_ring;
-    K.ep_rows = c->ep_rows + (int64_t)slot * c->ep_n * CBEV_EP_COUNT;
-    K.ep_count = c->ep_counts + slot;
-    K.ep_count_next = c->ep_counts + next;
-    K.ep_cap = c->ep_n;
-    c->step_count += 1;
-  }
-  const int wg4 = (n + 3) / 4;
-  const dim3 ego_grid((n + c->ego_ne - 1) / c->ego_ne);
-  const EgoPack pk = ego_pack(c->L);
-  // events as in cbev_step_repeat: 0 before substep 1, 1 after its actors kernel,
-  // 2 after the last substep's ego kernel, 3 after the raster
-  hipEvent_t* ev = nullptr;
-  if (c->prof_on && c->prof_n < CBEV_PROF_MAX) ev = c->prof_ev + 4 * c->prof_n++;
-  if (ev) HIP_TRY(hipEventRecord(ev[0], s));
-  if (c->C.actor_cap > 0)
-    hipLaunchKernelGGL(actors_mask_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n, active,
-                       (const uint8_t*)nullptr);
-  if (ev) HIP_TRY(hipEventRecord(ev[1], s));
-  hipLaunchKernelGGL(k_ego_mask<true>, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n, c->ego_ne,
-                     (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, active, reward, term, trunc,
-                     cause, info);
-  for (int j = 2; j <= repeat; ++j) {
-    if (c->C.actor_cap > 0)
-      hipLaunchKernelGGL(actors_mask_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n, active,
-                         (const uint8_t*)term);
-    hipLaunchKernelGGL(k_ego_mask<false>, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n,
-                       c->ego_ne, (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, active, reward,
-                       term, trunc, cause, info);
-  }
-  if (ev) HIP_TRY(hipEventRecord(ev[2], s));
-  launch_raster_mask(c, K, records, n, frames, active, prev_frames, s);
-  if (ev) HIP_TRY(hipEventRecord(ev[3], s));
-  HIP_TRY(hipGetLastError());
-  return CBEV_OK;
+  return step_chain(c, StepChain{STEP_MASKED, active, prev_frames, nullptr, 0}, records, n, actions, repeat, frames,
+                    reward, term, trunc, cause, info, stream);
 }
 
-// The masked step with a frame-stack head per env: cbev_step_masked's chain,
-// with k_ego_heads as substep 1's ego kernel (it advances the heads of the
-// active envs in place, once per call) and k_raster_heads as the raster (an
-// active env into ring[heads[e]][e], an inactive env's workgroups return at
-// once: nothing is copied).
+// The masked step with a frame-stack head per env.
 int cbev_step_heads(cbev_ctx* c, void* records, int n, const void* actions, const uint8_t* active, int repeat,
                     uint8_t* ring, int n_frames, uint8_t* heads, double* reward, uint8_t* term, uint8_t* trunc,
                     int32_t* cause, float* info, void* stream) {
@@ -5170,50 +5135,8 @@ int cbev_step_heads(cbev_ctx* c, void* records, int n, const void* actions, cons
     return set_err(CBEV_EINVAL, "repeat %d outside [1, %d]", repeat, CBEV_REPEAT_MAX);
   if (n_frames < 1 || n_frames > 255) return set_err(CBEV_EINVAL, "n_frames %d outside [1, 255]", n_frames);
   if (((uintptr_t)ring) & 15u) return set_err(CBEV_EINVAL, "ring must be 16-byte aligned");
-  if (!c->map_dev) return set_err(CBEV_ESTATE, "cbev_set_map not called");
-  if (n <= 0) return CBEV_OK;
-  if (c->stats && n > c->ep_n) return set_err(CBEV_EINVAL, "n %d exceeds the %d envs of the episode stats", n, c->ep_n);
-  CBEV_FLUSH(c);  // a deferred reset is launched first, as cbev_step_masked does
-  hipStream_t s = (hipStream_t)stream;
-  KArgs K = kargs(c);
-  c->last_term = term;
-  c->last_n = n;
-  if (n > c->seq_n) c->seq_n = n;
-  if (c->stats) {  // every substep's rows into this call's slot
-    const int slot = (int)(c->step_count % c->ep_ring), next = (slot + 1) % c->ep_ring;
-    K.ep_rows = c->ep_rows + (int64_t)slot * c->ep_n * CBEV_EP_COUNT;
-    K.ep_count = c->ep_counts + slot;
-    K.ep_count_next = c->ep_counts + next;
-    K.ep_cap = c->ep_n;
-    c->step_count += 1;
-  }
-  const int wg4 = (n + 3) / 4;
-  const dim3 ego_grid((n + c->ego_ne - 1) / c->ego_ne);
-  const EgoPack pk = ego_pack(c->L);
-  // events as in cbev_step_masked
-  hipEvent_t* ev = nullptr;
-  if (c->prof_on && c->prof_n < CBEV_PROF_MAX) ev = c->prof_ev + 4 * c->prof_n++;
-  if (ev) HIP_TRY(hipEventRecord(ev[0], s));
-  if (c->C.actor_cap > 0)
-    hipLaunchKernelGGL(actors_mask_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n, active,
-                       (const uint8_t*)nullptr);
-  if (ev) HIP_TRY(hipEventRecord(ev[1], s));
-  hipLaunchKernelGGL(k_ego_heads, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n, c->ego_ne,
-                     (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, active, reward, term, trunc,
-                     cause, info, heads, n_frames);
-  for (int j = 2; j <= repeat; ++j) {
-    if (c->C.actor_cap > 0)
-      hipLaunchKernelGGL(actors_mask_kernel(c->C), dim3(wg4), dim3(256), 0, s, K, (uint8_t*)records, n, active,
-                         (const uint8_t*)term);
-    hipLaunchKernelGGL(k_ego_mask<false>, ego_grid, dim3(256), (size_t)c->ego_lb, s, (uint8_t*)records, n,
-                       c->ego_ne, (int)c->L.record_bytes, pk.n0, pk.n, (int)c->L.raw_x, K, actions, active, reward,
-                       term, trunc, cause, info);
-  }
-  if (ev) HIP_TRY(hipEventRecord(ev[2], s));
-  launch_raster_heads(c, K, records, n, ring, n_frames, active, heads, s);
-  if (ev) HIP_TRY(hipEventRecord(ev[3], s));
-  HIP_TRY(hipGetLastError());
-  return CBEV_OK;
+  return step_chain(c, StepChain{STEP_HEADS, active, nullptr, heads, n_frames}, records, n, actions, repeat, ring,
+                    reward, term, trunc, cause, info, stream);
 }
 
 int cbev_reset(cbev_ctx* c, void* records, int n, const void* bank, int n_bank, const uint8_t* mask,
@@ -5228,15 +5151,8 @@ int cbev_reset(cbev_ctx* c, void* records, int n, const void* bank, int n_bank, 
   const size_t lb = raster_lds_bytes(c->P);
   hipStream_t s = (hipStream_t)stream;
   const int grid = n < RESET_WGS ? n : RESET_WGS;
-#define CBEV_LAUNCH_RESET(G_)                                                                                          \
-  hipLaunchKernelGGL(k_reset<G_>, dim3(grid), dim3(256), lb, s, K, (uint8_t*)records, n, (const uint8_t*)bank, n_bank,  \
-                     mask, bank_idx, bank_offset, frames, n_frames)
-  switch (c->P.size) {
-    case 64: CBEV_LAUNCH_RESET(1); break;
-    case 128: CBEV_LAUNCH_RESET(2); break;
-    default: CBEV_LAUNCH_RESET(4); break;
-  }
-#undef CBEV_LAUNCH_RESET
+  hipLaunchKernelGGL(CBEV_BY_SIZE(k_reset, c->P.size), dim3(grid), dim3(256), lb, s, K, (uint8_t*)records, n,
+                     (const uint8_t*)bank, n_bank, mask, bank_idx, bank_offset, frames, n_frames);
   HIP_TRY(hipGetLastError());
   return CBEV_OK;
 }
@@ -5250,11 +5166,8 @@ int cbev_bank_frames(cbev_ctx* c, const void* bank, int n_bank, uint8_t* frames,
   const size_t lb = raster_lds_bytes(c->P);
   hipStream_t s = (hipStream_t)stream;
   const int grid = n_bank < RESET_WGS ? n_bank : RESET_WGS;
-  switch (c->P.size) {
-    case 64: hipLaunchKernelGGL(k_bank_frames<1>, dim3(grid), dim3(256), lb, s, K, (const uint8_t*)bank, n_bank, frames); break;
-    case 128: hipLaunchKernelGGL(k_bank_frames<2>, dim3(grid), dim3(256), lb, s, K, (const uint8_t*)bank, n_bank, frames); break;
-    default: hipLaunchKernelGGL(k_bank_frames<4>, dim3(grid), dim3(256), lb, s, K, (const uint8_t*)bank, n_bank, frames); break;
-  }
+  hipLaunchKernelGGL(CBEV_BY_SIZE(k_bank_frames, c->P.size), dim3(grid), dim3(256), lb, s, K, (const uint8_t*)bank,
+                     n_bank, frames);
   HIP_TRY(hipGetLastError());
   return CBEV_OK;
 }
@@ -5272,8 +5185,7 @@ int cbev_reset_frames(cbev_ctx* c, void* records, int n, const void* bank, int n
   const int64_t pieces = (int64_t)n * (reset_pieces((int64_t)c->P.size * c->P.size) + reset_pieces(c->L.record_bytes));
   // grid cap for masked resets (the canonical reset of the envs that terminated):
   // 1024 measured best (config 2: 6.0 / 6.2 / 6.6 / 7.6 / 10.9 us at 1024 / 256 / 128 / 2048 / 4096)
-  const int cap = mask ? RESET_WGS : RESET_WGS;
-  const int grid = pieces >= cap ? cap : (int)((pieces + 7) & ~7);
+  const int grid = pieces >= RESET_WGS ? RESET_WGS : (int)((pieces + 7) & ~7);
   hipLaunchKernelGGL(k_reset_copy, dim3(grid), dim3(256), 0, (hipStream_t)stream, K, (uint8_t*)records, n,
                      (const uint8_t*)bank, n_bank, mask, bank_idx, bank_offset, bank_frames, frames, n_frames);
   HIP_TRY(hipGetLastError());

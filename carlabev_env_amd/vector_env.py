@@ -656,15 +656,28 @@ class CarlaBEVVectorEnv:
         return self._obs()
 
     def _launch_reset_masked(self, mask: torch.Tensor):
-        N, B = self.num_envs, self.bank.shape[0]
-        rec = self._p_step[0]
+        # the cached raw pointers, no flush from here: cbev_reset_masked applies a deferred reset itself
+        dst, n_frames = self._reset_dst(raw=True)
+        check(lib().cbev_reset_masked(self._ctx, self._p_step[0], self.num_envs, mask.data_ptr(), self._p_bank,
+                                      self.bank.shape[0], self._p_bank_frames, dst, n_frames, self._stream()),
+              "cbev_reset_masked")
+        self._finish_reset(mask)
+
+    def _reset_dst(self, raw: bool = False):
+        """(destination, slots) of a reset's frame: the render-size frame, 1, with a resize, else the
+        ring, F. raw: the cached address, not the tensor (self.ring applies a deferred reset first)."""
         if self.resize:
-            check(lib().cbev_reset_masked(self._ctx, rec, N, mask.data_ptr(), self._p_bank, B, self._p_bank_frames,
-                                          self._p_full, 1, self._stream()), "cbev_reset_masked")
+            return (self._p_full if raw else self.full), 1
+        return (self._p_ring if raw else self.ring), self.F
+
+    def _finish_reset(self, mask: torch.Tensor | None):
+        if self.resize:  # the reset frame of the masked envs (None: all) into every ring slot
             self._resize_into_ring(mask, all_slots=True)
-        else:
-            check(lib().cbev_reset_masked(self._ctx, rec, N, mask.data_ptr(), self._p_bank, B, self._p_bank_frames,
-                                          self._p_ring, self.F, self._stream()), "cbev_reset_masked")
+
+    def _ones_mask(self) -> torch.Tensor:
+        if self._all_mask is None:  # uint8 ones on the device, created once: every env selected
+            self._all_mask = torch.ones(self.num_envs, dtype=torch.uint8, device=self.device)
+        return self._all_mask
 
     def bank_rows_used(self) -> int:
         """Bank rows the masked resets (reset_terminated, reset_from_bank without
@@ -708,9 +721,7 @@ class CarlaBEVVectorEnv:
             mask = mask.reshape(N).to(device=self.device, dtype=torch.uint8).contiguous()
         if bank_idx is None:
             if mask is None:
-                if self._all_mask is None:
-                    self._all_mask = torch.ones(N, dtype=torch.uint8, device=self.device)
-                mask = self._all_mask
+                mask = self._ones_mask()
             obs = self._reset_masked(mask)
             self._clear_term(mask)
             return obs
@@ -718,15 +729,11 @@ class CarlaBEVVectorEnv:
         if bank_idx.numel() != N:
             raise ValueError(f"bank_idx has {bank_idx.numel()} entries, expected {N}")
         bank_idx = bank_idx.reshape(N).to(device=self.device, dtype=torch.int32).contiguous()
-        if self.resize:
-            check(lib().cbev_reset_frames(self._ctx, _ptr(self.records), N, _ptr(self.bank), B, _ptr(mask),
-                                          _ptr(bank_idx), 0, _ptr(self.bank_frames), _ptr(self.full), 1,
-                                          self._stream()), "cbev_reset_frames")
-            self._resize_into_ring(mask, all_slots=True)
-        else:
-            check(lib().cbev_reset_frames(self._ctx, _ptr(self.records), N, _ptr(self.bank), B, _ptr(mask),
-                                          _ptr(bank_idx), 0, _ptr(self.bank_frames), _ptr(self.ring), self.F,
-                                          self._stream()), "cbev_reset_frames")
+        dst, n_frames = self._reset_dst()
+        check(lib().cbev_reset_frames(self._ctx, _ptr(self.records), N, _ptr(self.bank), B, _ptr(mask),
+                                      _ptr(bank_idx), 0, _ptr(self.bank_frames), _ptr(dst), n_frames,
+                                      self._stream()), "cbev_reset_frames")
+        self._finish_reset(mask)
         self._clear_term(mask)
         if not self.auto_obs:
             return None
@@ -741,11 +748,10 @@ class CarlaBEVVectorEnv:
             raise ValueError(f"expected a ({N}, {self.rb}) uint8 tensor on {self.device}")
         records = records.contiguous()
         self._check_records(records, "load_scenes")
-        dst = self.full if self.resize else self.ring
+        dst, n_frames = self._reset_dst()
         check(lib().cbev_reset(self._ctx, _ptr(self.records), N, _ptr(records), N, None, None, 0, _ptr(dst),
-                               1 if self.resize else self.F, self._stream()), "cbev_reset")
-        if self.resize:
-            self._resize_into_ring(None, all_slots=True)
+                               n_frames, self._stream()), "cbev_reset")
+        self._finish_reset(None)
         self._clear_term(None)
 
     def _resize_into_ring(self, mask: torch.Tensor | None, all_slots: bool):
@@ -818,13 +824,10 @@ class CarlaBEVVectorEnv:
             bank_idx[idx] = np.arange(len(idx), dtype=np.int32)
             bidx = torch.from_numpy(bank_idx).to(self.device)
             m = torch.from_numpy(mask.astype(np.uint8)).to(self.device)
-            if self.resize:
-                check(lib().cbev_reset(self._ctx, _ptr(self.records), N, _ptr(staging), len(idx), _ptr(m), _ptr(bidx),
-                                       0, _ptr(self.full), 1, self._stream()), "cbev_reset")
-                self._resize_into_ring(m, all_slots=True)
-            else:
-                check(lib().cbev_reset(self._ctx, _ptr(self.records), N, _ptr(staging), len(idx), _ptr(m), _ptr(bidx),
-                                       0, _ptr(self.ring), self.F, self._stream()), "cbev_reset")
+            dst, n_frames = self._reset_dst()
+            check(lib().cbev_reset(self._ctx, _ptr(self.records), N, _ptr(staging), len(idx), _ptr(m), _ptr(bidx),
+                                   0, _ptr(dst), n_frames, self._stream()), "cbev_reset")
+            self._finish_reset(m)
             self._clear_term(m)
         obs = self._obs()
         infos = {}
@@ -888,41 +891,31 @@ class CarlaBEVVectorEnv:
         stream = self._stream()
         if self.per_env:
             # every step is cbev_step_heads; the plain one with the cached all-ones mask
-            if masked:
-                m = self._active_mask(active)
-            else:
-                if self._all_mask is None:
-                    self._all_mask = torch.ones(self.num_envs, dtype=torch.uint8, device=self.device)
-                m = self._all_mask.data_ptr()
+            m = self._active_mask(active) if masked else self._ones_mask().data_ptr()
             check(lib().cbev_step_heads(self._ctx, rec, self.num_envs, a.data_ptr(), m, self.action_repeat,
                                         self._p_ring, self.F, self.heads.data_ptr(), rew, term, trunc, cause, info,
                                         stream), "cbev_step_heads")
-            self._reset_pending = False
-            self._step_stream = stream.value or 0
-            self._stepped = True
-            if self.same_step:
-                self._autoreset(active is not None, stream)
-            return a
-        old = self.head
-        self.head = (self.head + 1) % self.F
-        frames = self._p_full if self.resize else self._p_ring + self.head * self._slot_bytes
-        if masked:
-            # an inactive env keeps its frame: the old head slot's into the new one (the
-            # render-size frame in place with a resize, which then resizes it again)
-            prev = self._p_full if self.resize else self._p_ring + old * self._slot_bytes
-            check(lib().cbev_step_masked(self._ctx, rec, self.num_envs, a.data_ptr(), self._active_mask(active),
-                                         self.action_repeat, prev, frames, rew, term, trunc, cause, info, stream),
-                  "cbev_step_masked")
-        elif self.action_repeat == 1:
-            check(lib().cbev_step(self._ctx, rec, self.num_envs, a.data_ptr(), frames, rew, term, trunc, cause, info,
-                                  stream), "cbev_step")
         else:
-            check(lib().cbev_step_repeat(self._ctx, rec, self.num_envs, a.data_ptr(), self.action_repeat, frames, rew,
-                                         term, trunc, cause, info, stream), "cbev_step_repeat")
+            old = self.head
+            self.head = (self.head + 1) % self.F
+            frames = self._p_full if self.resize else self._p_ring + self.head * self._slot_bytes
+            if masked:
+                # an inactive env keeps its frame: the old head slot's into the new one (the
+                # render-size frame in place with a resize, which then resizes it again)
+                prev = self._p_full if self.resize else self._p_ring + old * self._slot_bytes
+                check(lib().cbev_step_masked(self._ctx, rec, self.num_envs, a.data_ptr(), self._active_mask(active),
+                                             self.action_repeat, prev, frames, rew, term, trunc, cause, info, stream),
+                      "cbev_step_masked")
+            elif self.action_repeat == 1:
+                check(lib().cbev_step(self._ctx, rec, self.num_envs, a.data_ptr(), frames, rew, term, trunc, cause,
+                                      info, stream), "cbev_step")
+            else:
+                check(lib().cbev_step_repeat(self._ctx, rec, self.num_envs, a.data_ptr(), self.action_repeat, frames,
+                                             rew, term, trunc, cause, info, stream), "cbev_step_repeat")
         self._reset_pending = False  # taken by this step (or launched before it)
         self._step_stream = stream.value or 0  # the step's rows are waited for on this stream (StepInfos)
         self._stepped = True
-        if self.resize:
+        if self.resize:  # never with per-env heads
             self._resize_into_ring(None, all_slots=False)
         if self.same_step:
             self._autoreset(active is not None, stream)
