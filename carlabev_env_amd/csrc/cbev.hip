@@ -911,6 +911,12 @@ __device__ __forceinline__ double d_hero_delta(double v, float sa) {
   return d_radians((double)sa * steer_deg);
 }
 
+// tan(clip(delta)) of State.update (state.py:36-40), ahead of the chain
+__device__ __forceinline__ double hero_tan_delta(double v, float sa) {
+  const double max_steer = 30.0 * (CB_PI / 180.0);
+  return tan(d_clip(d_hero_delta(v, sa), -max_steer, max_steer));
+}
+
 // Per-env values k_ego computes ahead of the scalar chain, on separate waves:
 // cos / sin of the pre-update yaw (front axle and State.update) and
 // tan(clip(delta)) of State.update.
@@ -919,12 +925,23 @@ struct HeroPre {
   float g, sa, b;  // the decoded action (S1, for S3's thread)
 };
 
-// Ego update, part A (one thread per env): target index update, throttle /
-// brake, State.update, damping (BaseAgent.physics_step, hero.py:88-138).
-__device__ __forceinline__ void hero_env_a(const KArgs& K, DRec r, int e, const void* __restrict__ actions,
-                                           int bi, const HeroPre& hp, const float* gsb = nullptr) {
-  double* hd = r.hd;
+// Ego update, part A (one thread per env), in two functions that read and write
+// disjoint fields, so every caller compiles the same arithmetic from one text:
+//   hero_env_tidx  the target index update from stanley_control's target search
+//                  (bi: first arg-min, reduced by the workgroup); its steering
+//                  output is unused by the hero, so the physics never reads it
+//   hero_env_phys  clock, throttle / brake, the ACC low-pass, State.update,
+//                  damping, U_* (BaseAgent.physics_step, hero.py:88-138)
+// k_ego and its variants call them in turn (S3). The split step's head runs the
+// physics alone, on registers; the tail does the target search and the index
+// update beside the raster.
+__device__ __forceinline__ void hero_env_tidx(DRec r, int bi) {
   int32_t* hi = r.hi;
+  hi[CBEV_HI_TIDX] = hi[CBEV_HI_TIDX] >= bi ? hi[CBEV_HI_TIDX] : bi;
+}
+__device__ __forceinline__ void hero_env_phys(const KArgs& K, DRec r, int e, const void* __restrict__ actions,
+                                              const HeroPre& hp, const float* gsb = nullptr) {
+  double* hd = r.hd;
   float g, sa, b;
   if (gsb) {  // decoded ahead
     g = gsb[0];
@@ -938,9 +955,6 @@ __device__ __forceinline__ void hero_env_a(const KArgs& K, DRec r, int e, const 
   double s[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) s[k] = hd[CBEV_HD_X + k];
-  // stanley_control's target search (bi: first arg-min, reduced by the workgroup);
-  // its steering output is unused by the hero
-  hi[CBEV_HI_TIDX] = hi[CBEV_HI_TIDX] >= bi ? hi[CBEV_HI_TIDX] : bi;
   const double v = s[3];
   const int scale = K.P.scale;
   // BaseAgent.accelerate / steering / brake (hero.py:140-162)
@@ -3066,10 +3080,108 @@ __device__ __forceinline__ void ego_restage(uint8_t* lds, Src src, uint64_t bits
 //   ego_tail   S5-S7
 // k_ego runs both in one workgroup (WHOLE: the tail takes the front's LDS and
 // registers, one write-back at the end). The split step (cbev_set_split_step)
-// launches k_ego_head = the front with its own write-back, and the tail rides
-// in k_raster's launch as its leading workgroups (its own stage-in from the
-// records the head updated, the cheap S4 pieces it needs computed again), where
-// its latency-bound float64 chains run beside the render instead of before it.
+// launches k_ego_head = only what k_raster reads (S1, S3's physics, the render
+// set-up, vis_draw and a folded reset's record), and the tail rides in
+// k_raster's launch as its leading workgroups (its own stage-in from the
+// records the head updated, then S2, the index update, comfort and the cheap S4
+// pieces it needs), where its latency-bound float64 chains run beside the
+// render instead of before it.
+
+// S2: Controller.calc_target_index (stanley_controller.py:51-62),
+// np.argmin(np.hypot(dx, dy)) over (env, route point) pairs: the first smallest
+// hypot, in two passes as d_target_index_serial: the env's smallest squared
+// distance (a square is within a few ulp of hypot^2, so every index whose hypot
+// can reach the minimum has one within (1 + 1e-14) of it), then hypot over those
+// candidates only (almost always one point of the env) with the reference's
+// strict '<'. An env's tpe threads (a power of two, aligned: butterflies) take
+// its points sub, sub + tpe, ...; the first PF of a thread's points are loaded
+// ahead (load), the rest in the loops. One text for k_ego's front, which
+// searches from the record's pose before S3 updates it, and for the split
+// step's tail, which searches from the pose State.update kept in X1 / Y1 / YAW1
+// bit for bit.
+template <int PF>
+struct S2Search {
+  double x[PF], y[PF], hx, hy, yaw;
+  double fx, fy, bd;
+  int nr, bi;
+  // ipose: CBEV_HD_X or CBEV_HD_X1 (x, y, yaw follow each other in both)
+  __device__ __forceinline__ void load(const DRec& g, int ipose, int sub, int tpe, int route_cap) {
+    hx = g.hd[ipose];
+    hy = g.hd[ipose + 1];
+    yaw = g.hd[ipose + 2];
+    nr = g.hi[CBEV_HI_NROUTE];
+#pragma unroll
+    for (int j = 0; j < PF; ++j) {  // index clamped to the route capacity: no branch around a load
+      const int i = min(sub + j * tpe, route_cap - 1);
+      x[j] = g.cx[i];
+      y[j] = g.cy[i];
+    }
+  }
+  // each thread's candidate (bd, bi) among its own points
+  __device__ __forceinline__ void scan(const DRec& g, int sub, int tpe) {
+    double syaw, cyaw;
+    d_sincos(yaw, &syaw, &cyaw);
+    fx = hx + CB_WHEELBASE * cyaw;
+    fy = hy + CB_WHEELBASE * syaw;
+    double d2v[PF], m2 = INFINITY;
+#pragma unroll
+    for (int j = 0; j < PF; ++j) {
+      const int i = sub + j * tpe;
+      const double dx = fx - x[j], dy = fy - y[j];
+      d2v[j] = i < nr ? dx * dx + dy * dy : INFINITY;
+      m2 = d2v[j] < m2 ? d2v[j] : m2;  // NaN never wins
+    }
+    for (int i = sub + PF * tpe; i < nr; i += tpe) {  // routes past the prefetched points
+      const double dx = fx - g.cx[i], dy = fy - g.cy[i];
+      const double d2 = dx * dx + dy * dy;
+      m2 = d2 < m2 ? d2 : m2;
+    }
+    butterfly(tpe, [&](auto off) {
+      constexpr int O = decltype(off)::value;
+      const double q = peer_f64<O>(m2);
+      m2 = q < m2 ? q : m2;
+    });
+    const double lim = m2 * (1.0 + 1e-14);
+    bd = INFINITY;
+    bi = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < PF; ++j) {
+      const int i = sub + j * tpe;
+      if (d2v[j] <= lim) {
+        const double h = hypot(fx - x[j], fy - y[j]);
+        if (h < bd) {  // first minimum within this thread's (increasing) indices
+          bd = h;
+          bi = i;
+        }
+      }
+    }
+    for (int i = sub + PF * tpe; i < nr; i += tpe) {
+      const double dx = fx - g.cx[i], dy = fy - g.cy[i];
+      if (!(dx * dx + dy * dy <= lim)) continue;
+      const double h = hypot(dx, dy);
+      if (h < bd) {
+        bd = h;
+        bi = i;
+      }
+    }
+  }
+  // the env's first arg-min, in every one of its threads
+  __device__ __forceinline__ int reduce(int tpe) {
+    butterfly(tpe, [&](auto off) {  // smallest hypot, lowest index on ties
+      constexpr int O = decltype(off)::value;
+      const double qd = peer_f64<O>(bd);
+      const int qi = peer_i32<O>(bi);
+      if (qd < bd || (qd == bd && qi < bi)) {
+        bd = qd;
+        bi = qi;
+      }
+    });
+    return bi == 0x7fffffff ? 0 : bi;
+  }
+};
+// route points per thread the search loads ahead: the first 64 points of a
+// route at 16 envs per workgroup (128 / ne threads per env), 128 at 8
+constexpr int S2_PF = 8;
 
 // S5's route points per thread loaded ahead
 constexpr int S5_PF = 4;
@@ -3087,7 +3199,7 @@ struct EgoCarry {
 };
 // LDS of a k_ego workgroup: [ne] record slots, then (nslot == 2, contexts the
 // reset can fold into: no actor slots) [ne] bank-row slots, then the collision
-// scratch. The tail role has nslot == 1 and uses neither best nor rrow.
+// scratch. The tail role has nslot == 1 and does not use rrow.
 struct EgoLds {
   uint8_t* scr;  // [ne] collision scratch (from S4; the folded reset's mask bits before)
   HeroPre* pre;  // [ne]
@@ -3120,16 +3232,23 @@ __device__ __forceinline__ void ego_actor_load(EgoCarry& C, const DRec& g, int a
   C.pav = RAD(g, CBEV_AD_V, a);
   C.pasz = RAI(g, CBEV_AI_SIZE, a);
 }
-// S4's collision prologue of one env (one lane): S6's set point, the ego tile
-// load, the hero rect and the scratch S5 accumulates into; DRAW: with the vis
-// words the observation will draw (vis_draw <- vis, the front's)
+// S6's Stanley set point (scene_info, scene.py:206-225): the route point at the
+// target index, so after the index update (S3 in k_ego; behind S2 in the tail role)
+__device__ __forceinline__ void ego_set_point(const DRec& r, EgoCarry& C) {
+  const int tidx = r.hi[CBEV_HI_TIDX];
+  C.spx = r.cx[tidx];
+  C.spy = r.cy[tidx];
+}
+// S4's collision prologue of one env (one lane): the ego tile load, the hero
+// rect and the scratch S5 accumulates into; DRAW (k_ego): with S6's set point
+// and the vis words the observation will draw (vis_draw <- vis). The tail role
+// takes its set point once its own S2 has moved the target index, and the head
+// has drawn vis_draw.
 template <bool DRAW>
 __device__ __forceinline__ void ego_coll_prologue(const KArgs& K, const DRec& r, uint8_t* sk,
                                                   const CollScratchLayout& SL, EgoCarry& C) {
   const cbev_params& P = K.P;
-  const int tidx = r.hi[CBEV_HI_TIDX];  // after S3 (scene_info, scene.py:206-225)
-  C.spx = r.cx[tidx];
-  C.spy = r.cy[tidx];
+  if (DRAW) ego_set_point(r, C);
   const double x = r.hd[CBEV_HD_X], y = r.hd[CBEV_HD_Y];
   const int tx = (int)d_clip(rint(x), 0, P.map_w - 1), ty = (int)d_clip(rint(y), 0, P.map_h - 1);
   const int tile = d_map_texel(K, tx + P.pad, ty + P.pad);  // world.py:159-165
@@ -3147,14 +3266,13 @@ __device__ __forceinline__ void ego_coll_prologue(const KArgs& K, const DRec& r,
   I[CS_TILE] = tile;
 }
 
-// S0-S4 for the workgroup's envs. WHOLE (k_ego): the tail follows in the same
-// workgroup and gets its registers in C; returns false when the workgroup has no
-// env. Otherwise (k_ego_head) the records are written back here: HD, HI, the
-// vis group, and a reset env's remaining pieces.
+// S0-S4 for the workgroup's envs (k_ego and its variants): the tail follows in
+// the same workgroup and gets its registers in C; returns false when the
+// workgroup has no env.
 // GATE == EgoGate::Mask (k_ego_mask): the action of an env whose bit of `frozen`
 // is set is not decoded (a zero action instead), so it raises no error flag.
 enum class EgoGate { None, Term, Mask };
-template <bool WHOLE, EgoGate GATE = EgoGate::None>
+template <EgoGate GATE = EgoGate::None>
 __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ recs, int n, int ne, int st_rb,
                                           int st_n0, int st_n, int st_raw_x, const KArgs& K,
                                           const void* __restrict__ actions, EgoCarry& C, uint64_t frozen = 0ull) {
@@ -3180,39 +3298,24 @@ __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ re
   // are waited for precisely while the LDS-DMA of waves 2 and 3 stays in
   // flight). S2's inputs come from HBM into registers, issued first: the pose,
   // the route length and S2_PF route points per thread (128 / ne threads per
-  // env: the first 64 points at 16 envs per workgroup, 128 at 8; points beyond
-  // are loaded in the loop); each of an env's threads computes the yaw's cos /
-  // sin itself (the same d_sincos as S1), so S2 needs no barrier before it and
-  // runs under the staging instead of after it. With a folded reset pending they
-  // are loaded from the records speculatively, beside the mask read (most envs
-  // keep their record), and a reset env's threads load them again from its bank
-  // row once the mask is read.
+  // env; points beyond are loaded in the loop); each of an env's threads
+  // computes the yaw's cos / sin itself (the same d_sincos as S1), so S2 needs no
+  // barrier before it and runs under the staging instead of after it. With a
+  // folded reset pending they are loaded from the records speculatively, beside
+  // the mask read (most envs keep their record), and a reset env's threads load
+  // them again from its bank row once the mask is read.
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int S2_PF = 8;
   const int tpe2 = 128 / ne, s2k = tid / tpe2, s2sub = tid - s2k * tpe2;
   const bool s2 = wave <= 1 && s2k < ne_eff;
-  double s2x[S2_PF], s2y[S2_PF], s2hx = 0.0, s2hy = 0.0, s2yaw = 0.0;
-  int s2nr = 0;
+  S2Search<S2_PF> S2{};
   DRec s2g = bind_rec(src_rec(s2 ? s2k : 0), K.L, K.C);
-  auto s2_load = [&]() {
-    s2hx = s2g.hd[CBEV_HD_X];
-    s2hy = s2g.hd[CBEV_HD_Y];
-    s2yaw = s2g.hd[CBEV_HD_YAW];
-    s2nr = s2g.hi[CBEV_HI_NROUTE];
-#pragma unroll
-    for (int j = 0; j < S2_PF; ++j) {  // index clamped to the route capacity: no branch around a load
-      const int i = min(s2sub + j * tpe2, K.C.route_cap - 1);
-      s2x[j] = s2g.cx[i];
-      s2y[j] = s2g.cy[i];
-    }
-  };
-  if (s2) s2_load();
+  if (s2) S2.load(s2g, CBEV_HD_X, s2sub, tpe2, K.C.route_cap);
   // S5's targets (env tid / tpe, points sub, sub + tpe, ...): the first S5_PF of
   // a thread's route points, loaded now; the Stanley set point of S6's thread
   // (tid < ne) is loaded in S4 once S3 has moved the target index
   const int tpe5 = 256 / ne, k5 = tid / tpe5;
-  if (WHOLE && k5 < ne_eff) ego_t5_load(C, K, bind_rec(src_rec(k5), K.L, K.C), ne);
+  if (k5 < ne_eff) ego_t5_load(C, K, bind_rec(src_rec(k5), K.L, K.C), ne);
   // the env's terminations so far (lane k of wave 0 = env e0 + k, also S6's
   // thread): the folded reset's bank row, and counted up at S6 on termination
   const uint32_t tc0 = tid < ne_eff ? K.tcount[e0 + tid] : 0u;
@@ -3229,9 +3332,9 @@ __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ re
     ego_restage(lds + ne * pk.bytes, src, R.bits, ne_eff, st_n0, st_n, st_raw_x);
     if (s2 && ((R.bits >> s2k) & 1ull)) {  // a reset env's S2 / S5 inputs again, from its bank row
       s2g = bind_rec(src(s2k), K.L, K.C);
-      s2_load();
+      S2.load(s2g, CBEV_HD_X, s2sub, tpe2, K.C.route_cap);
     }
-    if (WHOLE && k5 < ne_eff && ((R.bits >> k5) & 1ull)) ego_t5_load(C, K, bind_rec(src(k5), K.L, K.C), ne);
+    if (k5 < ne_eff && ((R.bits >> k5) & 1ull)) ego_t5_load(C, K, bind_rec(src(k5), K.L, K.C), ne);
   }
   // env k's staged ranges: its record slot, or its bank-row slot when the folded reset takes it
   auto slot = [&](int k) -> uint8_t* { return lds + ((R.bits >> k) & 1ull ? ne + k : k) * pk.bytes; };
@@ -3246,13 +3349,10 @@ __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ re
   const int nres = __popcll(R.bits);
   uint4 rest_v = make_uint4(0, 0, 0, 0);
   int rest_k = -1, rest_o = 0;
-  auto rest_piece = [&](int q, int* k, int* o) {
-    *k = nth_set_bit(R.bits, q / rpp);
-    const int c = q % rpp;
-    *o = c < rsA ? (int)K.L.cx + 16 * c : 16 * (rsB0 + c - rsA);
-  };
   if ((int)threadIdx.x < nres * rpp) {
-    rest_piece(threadIdx.x, &rest_k, &rest_o);
+    rest_k = nth_set_bit(R.bits, threadIdx.x / rpp);
+    const int c = threadIdx.x % rpp;
+    rest_o = c < rsA ? (int)K.L.cx + 16 * c : 16 * (rsB0 + c - rsA);
     rest_v = *(const uint4*)(src(rest_k) + rest_o);
     asm volatile("" ::"v"(rest_v.x), "v"(rest_v.y), "v"(rest_v.z), "v"(rest_v.w));  // issued here, not sunk to S7
   }
@@ -3275,8 +3375,7 @@ __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ re
       pre[lane].b = ab;
       d_sincos(ghd[CBEV_HD_YAW], &pre[lane].syaw, &pre[lane].cyaw);
     } else {
-      const double max_steer = 30.0 * (CB_PI / 180.0);
-      pre[lane].tdelta = tan(d_clip(d_hero_delta(ghd[CBEV_HD_V], asa), -max_steer, max_steer));
+      pre[lane].tdelta = hero_tan_delta(ghd[CBEV_HD_V], asa);
     }
   }
   // the (env, actor) pair of S5 this thread takes first: its actor's fields are
@@ -3284,74 +3383,17 @@ __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ re
   const int A = K.C.actor_cap;
   C.pax = C.pay = C.payaw = C.pav = 0.0;
   C.pasz = 0;
-  if (WHOLE && tid < ne_eff * A) {
+  if (tid < ne_eff * A) {
     const int k = tid / A;
     ego_actor_load(C, bind_rec(src(k), K.L, K.C), tid - k * A);
   }
   CBEV_STAMP(3, 1);
-  // S2: Controller.calc_target_index (stanley_controller.py:51-62),
-  // np.argmin(np.hypot(dx, dy)): the first smallest hypot, in two passes as
-  // d_target_index_serial: the env's smallest squared distance (a square is
-  // within a few ulp of hypot^2, so every index whose hypot can reach the
-  // minimum has one within (1 + 1e-14) of it), then hypot over those candidates
-  // only (almost always one point of the env) with the reference's strict '<'
+  // S2
   if (s2) {
-    double syaw, cyaw;
-    d_sincos(s2yaw, &syaw, &cyaw);
-    const double fx = s2hx + CB_WHEELBASE * cyaw;
-    const double fy = s2hy + CB_WHEELBASE * syaw;
-    double d2v[S2_PF], m2 = INFINITY;
-#pragma unroll
-    for (int j = 0; j < S2_PF; ++j) {
-      const int i = s2sub + j * tpe2;
-      const double dx = fx - s2x[j], dy = fy - s2y[j];
-      d2v[j] = i < s2nr ? dx * dx + dy * dy : INFINITY;
-      m2 = d2v[j] < m2 ? d2v[j] : m2;  // NaN never wins
-    }
-    for (int i = s2sub + S2_PF * tpe2; i < s2nr; i += tpe2) {  // routes past the prefetched points
-      const double dx = fx - s2g.cx[i], dy = fy - s2g.cy[i];
-      const double d2 = dx * dx + dy * dy;
-      m2 = d2 < m2 ? d2 : m2;
-    }
-    butterfly(tpe2, [&](auto off) {
-      constexpr int O = decltype(off)::value;
-      const double q = peer_f64<O>(m2);
-      m2 = q < m2 ? q : m2;
-    });
-    const double lim = m2 * (1.0 + 1e-14);
-    double bd = INFINITY;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < S2_PF; ++j) {
-      const int i = s2sub + j * tpe2;
-      if (d2v[j] <= lim) {
-        const double h = hypot(fx - s2x[j], fy - s2y[j]);
-        if (h < bd) {  // first minimum within this thread's (increasing) indices
-          bd = h;
-          bi = i;
-        }
-      }
-    }
-    for (int i = s2sub + S2_PF * tpe2; i < s2nr; i += tpe2) {
-      const double dx = fx - s2g.cx[i], dy = fy - s2g.cy[i];
-      if (!(dx * dx + dy * dy <= lim)) continue;
-      const double h = hypot(dx, dy);
-      if (h < bd) {
-        bd = h;
-        bi = i;
-      }
-    }
+    S2.scan(s2g, s2sub, tpe2);
     CBEV_STAMP(3, 2);
-    butterfly(tpe2, [&](auto off) {  // smallest hypot, lowest index on ties
-      constexpr int O = decltype(off)::value;
-      const double qd = peer_f64<O>(bd);
-      const int qi = peer_i32<O>(bi);
-      if (qd < bd || (qd == bd && qi < bi)) {
-        bd = qd;
-        bi = qi;
-      }
-    });
-    if (s2sub == 0) best[s2k] = bi == 0x7fffffff ? 0 : bi;
+    const int bi = S2.reduce(tpe2);
+    if (s2sub == 0) best[s2k] = bi;
   }
   CBEV_STAMP(3, 3);
   __syncthreads();  // the staging has landed; S1 / S2 results in LDS
@@ -3360,7 +3402,8 @@ __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ re
   // S3
   if (tid < ne_eff) {
     const float gsb[3] = {pre[tid].g, pre[tid].sa, pre[tid].b};
-    hero_env_a(K, rec(tid), e0 + tid, actions, best[tid], pre[tid], gsb);
+    hero_env_tidx(rec(tid), best[tid]);
+    hero_env_phys(K, rec(tid), e0 + tid, actions, pre[tid], gsb);
   }
   __syncthreads();
   // S4
@@ -3374,34 +3417,18 @@ __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ re
       // a folded reset's bank row for k_raster (the reset frame into the other ring
       // slots), beside the fast bit it reads anyway: RS_FAST bits 1.. = row + 1
       if ((R.bits >> lane) & 1ull) rr.hi[CBEV_HI_RS_FAST] |= (rrow[lane] + 1) << 1;
-    } else if (WHOLE && wave == 3) {  // the updated yaw's cos / sin for the actors' TTCs (S5)
+    } else if (wave == 3) {  // the updated yaw's cos / sin for the actors' TTCs (S5)
       const double yaw = ((const double*)(slot(lane) + K.L.hd))[CBEV_HD_YAW];
       d_sincos(yaw, &pre[lane].syaw, &pre[lane].cyaw);
     } else if (wave == 0) {
-      const DRec r = rec(lane);
-      if (WHOLE) {
-        ego_coll_prologue<true>(K, r, scr + lane * SL.bytes, SL, C);
-      } else {
-        for (int w = 0; w < K.L.vis_words; ++w) r.vis_draw[w] = r.vis[w];
-      }
+      ego_coll_prologue<true>(K, rec(lane), scr + lane * SL.bytes, SL, C);
     }
   }
   __syncthreads();
   CBEV_STAMP(0, 3);
-  if (WHOLE) {  // written back after the tail
-    C.rest_v = rest_v;
-    C.rest_k = rest_k;
-    C.rest_o = rest_o;
-    return true;
-  }
-  // the head's write-back: all the raster reads, and the records the tail stages from
-  ego_stage_out(slot, recs, e0, ne_eff, K, pk);
-  if (rest_k >= 0) *(uint4*)(recs + (int64_t)(e0 + rest_k) * rb + rest_o) = rest_v;
-  for (int q = threadIdx.x + 256; q < nres * rpp; q += 256) {
-    int k, o;
-    rest_piece(q, &k, &o);
-    *(uint4*)(recs + (int64_t)(e0 + k) * rb + o) = *(const uint4*)(src(k) + o);
-  }
+  C.rest_v = rest_v;  // written back after the tail
+  C.rest_k = rest_k;
+  C.rest_o = rest_o;
   return true;
 }
 
@@ -3420,8 +3447,8 @@ __device__ __forceinline__ bool ego_front(uint8_t* lds, uint8_t* __restrict__ re
 #define CBEV_HI_BIT(n) (1ull << CBEV_HI_##n)
 constexpr uint64_t kRasterHi = CBEV_HI_BIT(NROUTE) | CBEV_HI_BIT(NACT) | CBEV_HI_BIT(NVEH) | CBEV_HI_BIT(NTL) |
                                ((2ull << CBEV_HI_RS_FAST) - (1ull << CBEV_HI_RS_XMIN));
-constexpr uint64_t kTailHi = CBEV_HI_BIT(S_PREV_VALID) | CBEV_HI_BIT(KSTEPS) | CBEV_HI_BIT(OFFROAD) |
-                             CBEV_HI_BIT(CAUSE) | CBEV_HI_BIT(TERM) | CBEV_HI_BIT(TRUNC) | CBEV_HI_BIT(TILE) |
+constexpr uint64_t kTailHi = CBEV_HI_BIT(TIDX) | CBEV_HI_BIT(HAS_PREV_COMFORT) | CBEV_HI_BIT(S_PREV_VALID) |
+                             CBEV_HI_BIT(KSTEPS) | CBEV_HI_BIT(OFFROAD) | CBEV_HI_BIT(CAUSE) | CBEV_HI_BIT(TERM) | CBEV_HI_BIT(TRUNC) | CBEV_HI_BIT(TILE) |
                              CBEV_HI_BIT(COLLIDED) | CBEV_HI_BIT(ACTOR_ID) | CBEV_HI_BIT(EP_LEN) | CBEV_HI_BIT(STEP) |
                              CBEV_HI_BIT(NACTSTATE);
 static_assert(CBEV_HI_COUNT <= 64 && (kRasterHi & kTailHi) == 0, "the tail writes a HI word the raster reads");
@@ -3501,11 +3528,19 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
   auto rec = [&](int k) { return bind_ego(slot(k), src(k), K, pk); };
   if (blockIdx.x == 0 && tid == 0 && K.ep_count_next != nullptr) *K.ep_count_next = 0;
   if (!WHOLE) {
-    // S0 again for the tail role: the staging (waves 2 and 3), then S5's
-    // prefetches, and under the staging the S4 pieces the tail needs, from the
-    // record in HBM (waves 0 and 1): the collision prologue, and the updated
-    // yaw's cos / sin for the actors' TTCs
+    // S0 again for the tail role: the staging (waves 2 and 3), then on waves 0
+    // and 1, which issue none of it, the loads of S2 and S5's prefetches, and
+    // under the staging S2 itself (the head ran the physics alone; the search
+    // starts from the pre-update pose State.update kept in X1 / Y1 / YAW1, the
+    // route from the record the head left) and the S4 pieces the tail needs,
+    // from the record in HBM: the collision prologue, and the updated yaw's
+    // cos / sin for the actors' TTCs
     ego_stage_in(lds, src, ne_eff, st_n0, st_n, st_raw_x);
+    const int tpe2 = 128 / ne, s2k = tid / tpe2, s2sub = tid - s2k * tpe2;
+    const bool s2 = wave <= 1 && s2k < ne_eff;
+    S2Search<S2_PF> S2{};
+    const DRec s2g = bind_rec(src(s2 ? s2k : 0), K.L, K.C);
+    if (s2) S2.load(s2g, CBEV_HD_X1, s2sub, tpe2, K.C.route_cap);
     const int tpe5 = 256 / ne, k5 = tid / tpe5;
     if (k5 < ne_eff) ego_t5_load(C, K, bind_rec(src(k5), K.L, K.C), ne);
     C.tc0 = tid < ne_eff ? K.tcount[e0 + tid] : 0u;
@@ -3524,7 +3559,25 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
         d_sincos(g.hd[CBEV_HD_YAW], &pre[lane].syaw, &pre[lane].cyaw);
       }
     }
-    __syncthreads();  // the staging has landed; the prologue's scratch in LDS
+    if (s2) {
+      S2.scan(s2g, s2sub, tpe2);
+      const int bi = S2.reduce(tpe2);
+      if (s2sub == 0) M.best[s2k] = bi;
+    }
+    __syncthreads();  // the staging has landed; the prologue's scratch and S2's result in LDS
+    // what k_ego does between S2 and S5 and the head left out: the target index
+    // update with S6's set point behind it (wave 0; lane k = S6's thread of env
+    // k) beside comfort + dist2goal (wave 1), on the staged record
+    if (lane < ne_eff) {
+      if (wave == 0) {
+        const DRec r = rec(lane);
+        hero_env_tidx(r, M.best[lane]);
+        ego_set_point(r, C);
+      } else if (wave == 1) {
+        hero_env_comfort(rec(lane));
+      }
+    }
+    __syncthreads();
   }
   const uint32_t tc0 = C.tc0;
   uint64_t frozen = 0ull;  // bit k: env e0 + k (each wave builds the workgroup's mask: ne <= 64)
@@ -3715,7 +3768,7 @@ __global__ __launch_bounds__(256) void k_ego(uint8_t* __restrict__ recs, int n, 
                                              int32_t* __restrict__ cause_out, float* __restrict__ info_out) {
   extern __shared__ __align__(16) uint8_t lds[];
   EgoCarry C;
-  if (!ego_front<true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C)) return;
+  if (!ego_front(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C)) return;
   ego_tail<true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out, trunc_out, cause_out,
                  info_out, C);
 }
@@ -3731,7 +3784,7 @@ __global__ __launch_bounds__(256) void k_ego_rep(uint8_t* __restrict__ recs, int
                                                  float* __restrict__ info_out) {
   extern __shared__ __align__(16) uint8_t lds[];
   EgoCarry C;
-  if (!ego_front<true>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C)) return;
+  if (!ego_front(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C)) return;
   ego_tail<true, EgoGate::Term>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out, trunc_out,
                                 cause_out, info_out, C);
 }
@@ -3778,7 +3831,7 @@ __device__ __forceinline__ void ego_mask_body(uint8_t* lds, uint8_t* __restrict_
     return;
   }
   EgoCarry C;
-  if (!ego_front<true, EgoGate::Mask>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C, frozen)) return;
+  if (!ego_front<EgoGate::Mask>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C, frozen)) return;
   ego_tail<true, EgoGate::Mask, FIRST>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, reward_out, term_out,
                                        trunc_out, cause_out, info_out, C, frozen);
 }
@@ -3803,16 +3856,197 @@ __global__ __launch_bounds__(256) void k_ego_heads(uint8_t* __restrict__ recs, i
                             trunc_out, cause_out, info_out, heads, n_frames);
 }
 
-// The split step's first launch: the front alone. It reads the previous step's
-// term bytes as the folded reset's mask; this step's are written by the tail in
-// the next launch of the stream, so the mask is read before it is overwritten.
-__global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, int n, int ne, int st_rb, int st_n0,
-                                                  int st_n, int st_raw_x, KArgs K,
+// The split step's first launch: only what the raster waits for. Of the
+// raster's record inputs (kRasterHi, the route, the actor poses, the lights,
+// vis_draw) the ego update produces two: RS_*, a function of the post-update
+// X / Y / YAW, and vis_draw, a copy of vis. The post-update pose is
+// State.update's, which reads the pre-update X, Y, YAW, V, ACC, TSPEED, the
+// action and S1's cos / sin / tan -- not the target search. So the head runs
+// S1, hero_env_phys and the render set-up per env on registers, with no record
+// staging, and leaves S2, the index update and comfort to the tail.
+//   wave 0, lane k   env e0 + k: cos / sin of the yaw, then (after the one
+//                    barrier) the physics, the render set-up and the write-back
+//                    of what they changed: the HD pieces X .. V1, ACC, U_*, T
+//                    and the HI words RS_XMIN .. RS_FAST
+//   wave 1, lane k   the action decoded and tan(clip(delta)) of the same env,
+//                    beside wave 0's sincos
+//   waves 2 and 3    vis_draw <- vis, a word per thread
+// Every load of a pass (pose, action, vis, and the folded reset's mask byte and
+// termination count) is issued before anything waits, so a kept env pays one
+// miss latency. The folded reset (KArgs::rmask: the previous step's term bytes,
+// read here before this step's tail overwrites them): every env computes from
+// its own record without waiting for the mask; only a workgroup that holds a
+// reset env runs a second pass, in which the reset envs' lanes compute again
+// from bank_row_of(e, tcount[e]) (its loads issued before the kept envs' chain
+// runs) while waves 2 and 3 copy that row over the whole record (vis_draw
+// taking the row's vis), so the tail and the raster find a complete record. A
+// reset lane stores after the pass's barrier, so after the copy. ne <= 64 envs per workgroup (a divisor of 64: staged_env0's placement).
+__global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, int n, int ne, int st_rb, KArgs K,
                                                   const void* __restrict__ actions) {
-  extern __shared__ __align__(16) uint8_t lds[];
-  EgoCarry C;
-  (void)ego_front<false>(lds, recs, n, ne, st_rb, st_n0, st_n, st_raw_x, K, actions, C);
+  __shared__ double sh_pre[2][3][64];  // per pass: cos, sin, tan of env k
+  __shared__ float sh_act[3][64];      // the decoded action of env k (wave 1, for wave 0's physics)
+  CBEV_STAMP(0, 0);
+  const int e0 = staged_env0(blockIdx.x, ne, n);
+  const int ne_eff = min(ne, n - e0);
+  if (ne_eff <= 0) return;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool on = lane < ne_eff;
+  const int e = e0 + (on ? lane : 0);
+  const int vw = K.L.vis_words;
+  const bool fold = K.rmask != nullptr;
+  // The env's mask byte and terminations so far: each wave issues them behind its
+  // own first loads and first uses them after pass 0's barrier (loaded
+  // unconditionally, from any valid address without a fold: loads pending at a
+  // branch's join, or merged there with a constant, are waited for on the spot).
+  const uint8_t* const mp = fold ? K.rmask + e : recs;
+  uint32_t mb = 0u, tc = 0u;
+  double hd[CBEV_HD_COUNT] = {};  // wave 0: the env's record fields in registers (constant indices only)
+  int32_t hi[CBEV_HI_COUNT] = {};
+  DRec r{};
+  r.hd = hd;
+  r.hi = hi;
+  constexpr int NIN = 7;  // X, Y, YAW, V, ACC, TSPEED, T
+  auto load_in = [&](const uint8_t* src, double* in) {
+    const double* g = (const double*)(src + K.L.hd);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) in[k] = g[CBEV_HD_X + k];
+    in[4] = g[CBEV_HD_ACC];
+    in[5] = g[CBEV_HD_TSPEED];
+    in[6] = g[CBEV_HD_T];
+  };
+  // wave 0 after a pass's barrier: the physics and the render set-up from `in`
+  auto chain = [&](int pass, const double* in) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) hd[CBEV_HD_X + k] = in[k];
+    hd[CBEV_HD_ACC] = in[4];
+    hd[CBEV_HD_TSPEED] = in[5];
+    hd[CBEV_HD_T] = in[6];
+    HeroPre hp;
+    hp.cyaw = sh_pre[pass][0][lane];
+    hp.syaw = sh_pre[pass][1][lane];
+    hp.tdelta = sh_pre[pass][2][lane];
+    const float act3[3] = {sh_act[0][lane], sh_act[1][lane], sh_act[2][lane]};
+    hero_env_phys(K, r, e, actions, hp, act3);
+    hero_env_render_setup(K, r);
+  };
+  double in0[NIN] = {}, in1[NIN] = {}, v0 = 0.0, v1 = 0.0;
+  float sa = 0.0f;
+  const uint8_t* const own = recs + (int64_t)e * st_rb;
+  // pass 0, every env from its own record
+  if (wave == 0) {
+    if (on) {
+      load_in(own, in0);
+      mb = *mp;
+      tc = K.tcount[e];
+      d_sincos(in0[2], &sh_pre[0][1][lane], &sh_pre[0][0][lane]);
+    }
+  } else if (wave == 1) {
+    if (on) {
+      v0 = ((const double*)(own + K.L.hd))[CBEV_HD_V];
+      mb = *mp;
+      tc = K.tcount[e];
+      float g, b;
+      d_decode_action(K, actions, e, &g, &sa, &b);  // the table lookup behind the index: on this wave alone
+      sh_act[0][lane] = g;
+      sh_act[1][lane] = sa;
+      sh_act[2][lane] = b;
+      sh_pre[0][2][lane] = hero_tan_delta(v0, sa);
+    }
+  } else {
+    mb = *mp;
+    tc = K.tcount[e];
+    // vis_draw <- vis of the kept envs (a reset env's comes with its bank row)
+    for (int q = tid - 128; q < ne_eff * vw; q += 128) {
+      const int k = q / vw, w = q - k * vw;
+      uint8_t* g = recs + (int64_t)(e0 + k) * st_rb + K.L.vis;
+      const uint32_t v = ((const uint32_t*)g)[w];
+      if (!(fold && K.rmask[e0 + k] != 0)) ((uint32_t*)g)[vw + w] = v;
+    }
+  }
+  __syncthreads();  // cos / sin / tan and the action in LDS
+  CBEV_STAMP(0, 1);
+  const bool reset = fold && on && mb != 0u;
+  const uint64_t rbits = __ballot(reset);  // lane k = env e0 + k in every wave: the same bits, uniform branches
+  // pass 1's inputs of the reset envs, issued before the kept envs' chain runs
+  const int row = reset ? bank_row_of(e, tc, K.rstride, K.rn_bank) : 0;
+  const uint8_t* const bank = K.rbank + (int64_t)row * st_rb;
+  if (wave == 0 && reset) load_in(bank, in1);
+  if (wave == 1 && reset) v1 = ((const double*)(bank + K.L.hd))[CBEV_HD_V];
+  if (wave == 0 && on && !reset) chain(0, in0);
+  if (rbits != 0ull) {
+    if (wave == 0) {
+      if (reset) {
+        // first touched here: arithmetic on them hoisted to the loads would be
+        // waited for ahead of the kept envs' chain
+#pragma unroll
+        for (int k = 0; k < NIN; ++k) asm volatile("" : "+v"(in1[k]));
+        d_sincos(in1[2], &sh_pre[1][1][lane], &sh_pre[1][0][lane]);
+      }
+    } else if (wave == 1) {
+      if (reset) sh_pre[1][2][lane] = hero_tan_delta(v1, sa);
+    } else {
+      // the reset envs' records from their bank rows, 16-byte pieces, two per thread
+      // in flight; a piece that overlaps vis_draw word by word, its vis_draw words
+      // from the row's vis
+      const int np = st_rb / 16, total = __popcll(rbits) * np;
+      const int d0 = (int)K.L.vis + 4 * vw, d1 = d0 + 4 * vw;
+      auto piece = [&](int q, const uint8_t** b, uint8_t** g, int* o) {  // every lane: the shuffle
+        const int j = q < total ? q / np : 0, k = nth_set_bit(rbits, j);
+        *o = 16 * (q - j * np);
+        *b = K.rbank + (int64_t)__shfl(row, k) * st_rb + *o;
+        *g = recs + (int64_t)(e0 + k) * st_rb + *o;
+      };
+      auto by_word = [&](const uint8_t* b, uint8_t* g, int o) {
+        for (int w = 0; w < 16; w += 4)
+          *(uint32_t*)(g + w) = *(const uint32_t*)(b + w - (o + w >= d0 && o + w < d1 ? 4 * vw : 0));
+      };
+      for (int base = tid - 128; base - (tid - 128) < total; base += 256) {  // uniform trip count
+        const uint8_t *b0, *b1;
+        uint8_t *g0, *g1;
+        int o0, o1;
+        piece(base, &b0, &g0, &o0);
+        piece(base + 128, &b1, &g1, &o1);
+        const bool a0 = base < total, a1 = base + 128 < total;
+        const bool w0 = o0 + 16 <= d0 || o0 >= d1, w1 = o1 + 16 <= d0 || o1 >= d1;
+        uint4 x0 = make_uint4(0, 0, 0, 0), x1 = x0;
+        if (a0 && w0) x0 = *(const uint4*)b0;
+        if (a1 && w1) x1 = *(const uint4*)b1;
+        if (a0 && w0) *(uint4*)g0 = x0;
+        if (a1 && w1) *(uint4*)g1 = x1;
+        if (a0 && !w0) by_word(b0, g0, o0);
+        if (a1 && !w1) by_word(b1, g1, o1);
+      }
+    }
+    __syncthreads();  // pass 1's cos / sin / tan in LDS; the bank rows have been copied
+    if (wave == 0 && reset) chain(1, in1);
+  }
+  CBEV_STAMP(0, 2);
+  if (wave == 0 && on) {
+    if (reset) {
+      // the bank row for k_raster (the reset frame into the other ring slots), beside
+      // the fast bit it reads anyway: RS_FAST bits 1.. = row + 1
+      hi[CBEV_HI_RS_FAST] |= (row + 1) << 1;
+      if (K.stats != nullptr) K.stats[e].t0 = (double)wall_clock64();  // the episode's start
+    }
+    uint8_t* g = recs + (int64_t)e * st_rb;
+    double* ohd = (double*)(g + K.L.hd);
+    int32_t* ohi = (int32_t*)(g + K.L.hi);
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) *(double2*)(ohd + CBEV_HD_X + k) = make_double2(hd[CBEV_HD_X + k], hd[CBEV_HD_X + k + 1]);
+    ohd[CBEV_HD_ACC] = hd[CBEV_HD_ACC];
+    *(double2*)(ohd + CBEV_HD_U_GAS) = make_double2(hd[CBEV_HD_U_GAS], hd[CBEV_HD_U_STEER]);
+    *(double2*)(ohd + CBEV_HD_U_BRAKE) = make_double2(hd[CBEV_HD_U_BRAKE], hd[CBEV_HD_U_DELTA]);
+    ohd[CBEV_HD_T] = hd[CBEV_HD_T];
+#pragma unroll
+    for (int k = CBEV_HI_RS_XMIN; k <= CBEV_HI_RS_FAST; ++k) ohi[k] = hi[k];
+  }
+  CBEV_STAMP(0, 3);
 }
+constexpr int HEAD_NE_DEFAULT = 16;
+static_assert(CBEV_HD_X % 2 == 0 && CBEV_HD_U_GAS % 2 == 0 && CBEV_HD_U_BRAKE == CBEV_HD_U_GAS + 2 &&
+                  CBEV_HD_U_DELTA == CBEV_HD_U_GAS + 3,
+              "k_ego_head stores X .. V1 and U_* as 16-byte pieces");
 
 // k_ego's tail as k_raster's leading workgroups (cbev_set_split_step)
 struct TailArgs {
@@ -4365,6 +4599,7 @@ struct cbev_ctx {
   int ego_ne;            // k_ego: envs per workgroup
   int ego_lb;            // k_ego: dynamic LDS bytes per workgroup
   int tail_ne;           // k_raster's tail role: envs per workgroup (0: the split step is not supported)
+  int head_ne;           // k_ego_head: envs per workgroup
   int split;             // cbev_set_split_step: k_ego_head, then k_raster with the tail
   int obs_h, obs_w;   // wrapped frame size (ResizeObservation); == size when not resizing
   void* area_dev;     // INTER_AREA tables of cbev_set_obs_size
@@ -4417,6 +4652,14 @@ static int ego_ne_for(int per_env, int actor_cap) {
   ne = ne >= 64 ? 64 : ne >= 32 ? 32 : ne >= 16 ? 16 : ne >= 8 ? 8 : 4;
   while (ne > 4 && ne * per_env > budget) ne >>= 1;
   return ne * per_env > budget ? 0 : ne;
+}
+
+// Envs per k_ego_head workgroup (a lane per env in each of its waves): a divisor
+// of 64 not above CBEV_HEAD_NE (default HEAD_NE_DEFAULT, DESIGN section 3 "The thin head").
+static int head_ne_for() {
+  const char* v = getenv("CBEV_HEAD_NE");
+  const int ne = v ? atoi(v) : HEAD_NE_DEFAULT;
+  return ne >= 64 ? 64 : ne >= 32 ? 32 : ne >= 16 ? 16 : ne >= 8 ? 8 : 4;
 }
 
 static thread_local std::string g_err;
@@ -4558,13 +4801,15 @@ static void launch_raster(const cbev_ctx* c, void (*k)(A), int n, int ntail, hip
   hipLaunchKernelGGL(k, dim3(grid), dim3(kRasterNT), raster_lds_bytes(c->P), s, args);
 }
 // Envs per workgroup of k_raster's tail role: the largest group size not above
-// k_ego's (so CBEV_EGO_NE holds) whose record slots, collision scratch and
-// HeroPre fit the raster's LDS, whose size and residency stay what they are.
+// k_ego's (so CBEV_EGO_NE holds) whose record slots, collision scratch, HeroPre
+// and S2 result (best) fit the raster's LDS, whose size and residency stay what
+// they are.
 // 0: none fits, or S = 64, where k_raster<1> targets 8 waves per SIMD and the
 // tail would spill: those contexts keep the unsplit k_ego.
 static int tail_ne_for(const cbev_params& P, const cbev_caps& C, const cbev_layout& L, int ego_ne) {
   if (P.size == 64) return 0;
-  const size_t per_env = (size_t)ego_pack(L).bytes + coll_scratch_layout(C, L.vis_words).bytes + sizeof(HeroPre);
+  const size_t per_env =
+      (size_t)ego_pack(L).bytes + coll_scratch_layout(C, L.vis_words).bytes + sizeof(HeroPre) + sizeof(int);
   for (int ne = ego_ne; ne >= 4; ne >>= 1)
     if (ne * per_env <= raster_lds_bytes(P)) return ne;
   return 0;
@@ -4743,6 +4988,7 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
   c->ego_lb = ego_ne * per_env;
   c->tail_ne = tail_ne_for(P, *caps, lay, ego_ne);
   c->split = c->tail_ne > 0;  // the default where supported (cbev_set_split_step)
+  c->head_ne = head_ne_for();
   SgTables T;
   build_sg_tables(&T);
   hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_sg), &T, sizeof T);
@@ -4766,8 +5012,6 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
   c->obs_h = c->obs_w = P.size;
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)k_ego, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_ego_head, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)k_ego_rep, hipFuncAttributeMaxDynamicSharedMemorySize, c->ego_lb);
   if (e == hipSuccess)
@@ -5009,9 +5253,10 @@ int cbev_step(cbev_ctx* c, void* records, int n, const void* actions, uint8_t* f
   if (R.ev) HIP_TRY(hipEventRecord(R.ev[1], R.s));
   TailArgs T{};
   if (c->split) {
-    // the front, then the raster's launch with the tail as its leading workgroups
+    // the head, then the raster's launch with the tail as its leading workgroups
     // (a multiple of 8 of them: the XCD placement of both roles stays)
-    launch_ego(c, k_ego_head, R, records, n, actions);
+    hipLaunchKernelGGL(k_ego_head, dim3((n + c->head_ne - 1) / c->head_ne), dim3(256), 0, R.s, (uint8_t*)records, n,
+                       c->head_ne, (int)c->L.record_bytes, R.K, actions);
     const EgoPack pk = ego_pack(c->L);
     T = TailArgs{((n + c->tail_ne - 1) / c->tail_ne + 7) & ~7, c->tail_ne, (int)c->L.record_bytes, pk.n0, pk.n,
                  (int)c->L.raw_x, reward, term, trunc, cause, info};
