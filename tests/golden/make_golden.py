@@ -18,6 +18,10 @@ Every vector set names the reference function it captures:
   route_geom.npz     compute_route_progress / cumulative_lengths / lateral_error
                                                       carl_reward_fn.py:20-58, control/utils.py:165-197
   seeds.json         derive_seed / build_rng_bundle   src/randomness.py:13-65
+
+Written by the other scripts of this folder:
+  episodes.npz, episodes.json   whole episodes of CarlaBEV.reset / CarlaBEV.step
+                                (make_golden_episodes.py)    envs/carlabev.py:96-231
 """
 from __future__ import annotations
 
