@@ -76,6 +76,10 @@ def lib():
     L.cbev_reset_pending.restype = _I
     L.cbev_set_split_step.argtypes = [_P, _I]
     L.cbev_set_split_step.restype = _I
+    L.cbev_set_reset_preview.argtypes = [_P, _I]
+    L.cbev_set_reset_preview.restype = _I
+    L.cbev_reset_preview_counts.argtypes = [_P, _P]
+    L.cbev_reset_preview_counts.restype = _I
     L.cbev_flush.argtypes = [_P]
     L.cbev_flush.restype = _I
     L.cbev_expand_obs.argtypes = [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]
@@ -133,7 +137,8 @@ EXPORTED_SYMBOLS = ("cbev_abi_version", "cbev_params_size", "cbev_layout_of", "c
                     "cbev_profile_raster", "cbev_error_flags", "cbev_set_episode_stats", "cbev_episode_slot",
                     "cbev_wall_clock_hz", "cbev_termination_count", "cbev_pack_frames", "cbev_unpack_frames",
                     "cbev_expand_obs_typed", "cbev_unpack_obs", "cbev_set_split_step", "cbev_step_repeat",
-                    "cbev_step_masked", "cbev_step_heads", "cbev_expand_obs_heads", "cbev_final_frames")
+                    "cbev_step_masked", "cbev_step_heads", "cbev_expand_obs_heads", "cbev_final_frames",
+                    "cbev_set_reset_preview", "cbev_reset_preview_counts")
 
 REPEAT_MAX = 64  # CBEV_REPEAT_MAX (include/cbev.h)
 

@@ -3500,7 +3500,8 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
                                          int st_n0, int st_n, int st_raw_x, const KArgs& K,
                                          double* __restrict__ reward_out, uint8_t* __restrict__ term_out,
                                          uint8_t* __restrict__ trunc_out, int32_t* __restrict__ cause_out,
-                                         float* __restrict__ info_out, EgoCarry& C, uint64_t frozen_in = 0ull) {
+                                         float* __restrict__ info_out, EgoCarry& C, uint64_t frozen_in = 0ull,
+                                         const PvArgs* pvw = nullptr) {
   constexpr bool GATED = GATE != EgoGate::None;
   constexpr bool ACCUM = GATE == EgoGate::Term || (GATE == EgoGate::Mask && !FIRST);
   const int e0 = staged_env0(blockIdx.x, ne, n);
@@ -3723,6 +3724,8 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
   __syncthreads();
   CBEV_STAMP(1, 1);
   // S6
+  int trow1 = 0;          // the preview's row + 1 of an env this lane terminates
+  uint32_t touched = 0u;  // the row's lines, loaded for the caches alone
   if (tid < ne_eff && !(GATED && ((frozen >> tid) & 1ull))) {
     const DRec r = rec(tid);
     CollPre cp = coll_reduce_serial(scr + tid * SL.bytes, SL, r.hi[CBEV_HI_NACT], r.hi[CBEV_HI_NRAW]);
@@ -3732,15 +3735,57 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
     if (ACCUM) rsum = reward_out[e0 + tid];  // r1 + .. + r(j-1)
     collide_env(K, r, e0 + tid, cp, reward_out, term_out, trunc_out, cause_out, info_out);
     if (ACCUM) reward_out[e0 + tid] = rsum + r.hd[CBEV_HD_REWARD];
-    if (r.hi[CBEV_HI_TERM]) K.tcount[e0 + tid] = tc0 + 1u;  // the next reset's bank row moves on
+    if (r.hi[CBEV_HI_TERM]) {
+      K.tcount[e0 + tid] = tc0 + 1u;  // the next reset's bank row moves on
+      // the reset preview: that row is known here, a step before k_ego_head needs
+      // it; its inputs go where the head loads them in its first round
+      if (GATE == EgoGate::None && pvw != nullptr && K.rbank != nullptr && pvw->tag != 0u) {
+        const int row = bank_row_of(e0 + tid, tc0 + 1u, K.rstride, K.rn_bank);
+        const double* g = (const double*)(K.rbank + (int64_t)row * st_rb + K.L.hd);
+        RPreview* const pv = pvw->pv + (e0 + tid);
+        const double x = g[CBEV_HD_X], y = g[CBEV_HD_Y], yaw = g[CBEV_HD_YAW], v = g[CBEV_HD_V];
+        const double acc = g[CBEV_HD_ACC], ts = g[CBEV_HD_TSPEED], t = g[CBEV_HD_T];
+        double2* const o = (double2*)pv;
+        o[0] = make_double2(x, y);
+        o[1] = make_double2(yaw, v);
+        o[2] = make_double2(acc, ts);
+        union {
+          uint32_t u[2];
+          double d;
+        } w;
+        w.u[0] = (uint32_t)row + 1u;
+        w.u[1] = pvw->tag;
+        o[3] = make_double2(t, w.d);
+        trow1 = row + 1;
+      }
+    }
   } else if (GATE == EgoGate::Mask && FIRST && tid < ne_eff) {
     reward_out[e0 + tid] = 0.0;  // an inactive env's reward of this agent step
+  }
+  // The rest of such a row, for the head's record copy: wave 0 (S6's lanes are its
+  // first ne_eff) loads a word of each of the row's 128-byte lines, a line per lane,
+  // so that the next launch finds them in this XCD's L2 and their pages translated.
+  // Nothing uses the words: they are waited for at the end of the role.
+  if (!WHOLE && GATE == EgoGate::None && wave == 0 && pvw != nullptr && K.rbank != nullptr && pvw->tag != 0u) {
+    uint32_t t0 = 0u, t1 = 0u;
+    for (uint64_t tb = __ballot(trow1 != 0); tb != 0ull; tb &= tb - 1ull) {
+      const int row = __shfl(trow1, __builtin_ctzll(tb)) - 1;
+      const uint8_t* const b = K.rbank + (int64_t)row * st_rb;
+      // both loads of every lane unconditional and in flight together (a lane past the
+      // row's lines loads its last word, as every lane's second load does: the row's last
+      // line, wherever the row starts in it); a row's lines past the 64th, a loop more
+      t0 |= *(const uint32_t*)(b + min(128 * lane, st_rb - 4));
+      t1 |= *(const uint32_t*)(b + st_rb - 4);
+      for (int o = 128 * (64 + lane); o < st_rb; o += 128 * 64) t1 |= *(const uint32_t*)(b + o);
+    }
+    touched = t0 | t1;
   }
   __syncthreads();
   CBEV_STAMP(1, 2);
   // S7
   if (!WHOLE) {
     ego_tail_out(lds, recs, e0, ne_eff, K, pk);
+    asm volatile("" ::"v"(touched));
     CBEV_STAMP(1, 3);
     return;
   }
@@ -3875,15 +3920,34 @@ __global__ __launch_bounds__(256) void k_ego_heads(uint8_t* __restrict__ recs, i
 // termination count) is issued before anything waits, so a kept env pays one
 // miss latency. The folded reset (KArgs::rmask: the previous step's term bytes,
 // read here before this step's tail overwrites them): every env computes from
-// its own record without waiting for the mask; only a workgroup that holds a
-// reset env runs a second pass, in which the reset envs' lanes compute again
-// from bank_row_of(e, tcount[e]) (its loads issued before the kept envs' chain
-// runs) while waves 2 and 3 copy that row over the whole record (vis_draw
-// taking the row's vis), so the tail and the raster find a complete record. A
-// reset lane stores after the pass's barrier, so after the copy. ne <= 64 envs per workgroup (a divisor of 64: staged_env0's placement).
+// its own record without waiting for the mask. In a workgroup that holds a
+// reset env, waves 2 and 3 copy the env's bank row bank_row_of(e, tcount[e])
+// over the record (vis_draw taking the row's vis), so the tail and the raster
+// find a complete record. The copy leaves out the words wave 0 stores at the end
+// (head_word), so the two write disjoint bytes and nothing orders them: no
+// barrier stands between the copy and wave 0's stores.
+// PV (the host launches it when the step may take previews, PvArgs::acc != 0):
+// in the first round, lane ne + k of waves 0 and 1 (the env lanes again, in a
+// second round, at ne = 64) loads env k's preview entry and computes cos / sin /
+// tan of its yaw and speed beside the env lanes, into sh_pre[1] and sh_pin. After
+// the barrier a reset lane whose entry carries the accepted tag and the row the
+// lane computes itself (`fast`) takes those inputs, and the chain runs once for
+// kept and fast lanes together. Every other reset lane (`slow`; all of them
+// without PV) computes in a second pass from the bank row, its loads issued
+// before the others' chain runs, behind a second barrier that only a workgroup
+// with a slow lane reaches. Wave 0 clears the tag of every accepted entry at the
+// end, after its whole chain; every wave issued the load of its copy of the tag
+// in the first round, long before, and a CU's requests reach its vector cache in
+// order, so no wave sees the cleared tag. Were one to see it, it would compute
+// `slow` where wave 0 computed `fast` and go to a second barrier wave 0 never
+// reaches: that barrier is released when wave 0 ends, and the records are the
+// same, because the copy leaves out wave 0's words whatever `fast` is.
+// ne <= 64 envs per workgroup (a divisor of 64: staged_env0's placement).
+template <bool PV>
 __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, int n, int ne, int st_rb, KArgs K,
-                                                  const void* __restrict__ actions) {
-  __shared__ double sh_pre[2][3][64];  // per pass: cos, sin, tan of env k
+                                                  const void* __restrict__ actions, PvArgs V) {
+  __shared__ double sh_pre[2][3][64];  // cos, sin, tan of env k: [0] from its record, [1] from its preview or (pass 1) its bank row
+  __shared__ double sh_pin[7][64];     // the preview's inputs of env k (wave 0's preview lanes, for its env lanes)
   __shared__ float sh_act[3][64];      // the decoded action of env k (wave 1, for wave 0's physics)
   CBEV_STAMP(0, 0);
   const int e0 = staged_env0(blockIdx.x, ne, n);
@@ -3893,14 +3957,34 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool on = lane < ne_eff;
   const int e = e0 + (on ? lane : 0);
-  const int vw = K.L.vis_words;
-  const bool fold = K.rmask != nullptr;
-  // The env's mask byte and terminations so far: each wave issues them behind its
-  // own first loads and first uses them after pass 0's barrier (loaded
+  // The kernel arguments the first round addresses with, in registers at one point:
+  // their kernarg loads are issued as one batch at the kernel's entry (left to
+  // their first uses, a second batch waited behind the first, a cold miss more).
+  // Every later use goes through the statement's outputs, so none of the loads can
+  // be left behind it.
+  const uint8_t* rmask = K.rmask;
+  const RPreview* pvb = V.pv;
+  const uint32_t* tcnt = K.tcount;
+  int vw = K.L.vis_words;
+  asm volatile("" : "+s"(rmask), "+s"(pvb), "+s"(tcnt), "+s"(vw));
+  const bool fold = rmask != nullptr;
+  // The env's mask byte, terminations so far and preview tag: each wave issues them
+  // behind its own first loads and first uses them after pass 0's barrier (loaded
   // unconditionally, from any valid address without a fold: loads pending at a
   // branch's join, or merged there with a constant, are waited for on the spot).
-  const uint8_t* const mp = fold ? K.rmask + e : recs;
+  const uint8_t* const mp = fold ? rmask + e : recs;
+  const RPreview* const pt = pvb + (fold ? e : 0);
   uint32_t mb = 0u, tc = 0u;
+  uint2 ptag = make_uint2(0u, 0u);  // the preview's row + 1 and tag
+  // The preview of env k rides beside the envs' own pass: where the wave has the
+  // lanes (2 ne <= 64), lane ne + k of waves 0 and 1 computes env k's cos / sin /
+  // tan from the preview in the same instructions as lane k does from the record;
+  // at ne = 64 the env lanes run the trigonometry a second round.
+  const int pvl = PV && 2 * ne <= 64 ? ne : 0;
+  const int kp = lane - pvl;  // the env whose preview this lane carries
+  const bool isp = PV && kp >= 0 && kp < ne_eff;
+  const RPreview* const pp = pvb + (fold ? e0 + (isp ? kp : 0) : 0);
+  const int nround = !PV || pvl ? 1 : 2;
   double hd[CBEV_HD_COUNT] = {};  // wave 0: the env's record fields in registers (constant indices only)
   int32_t hi[CBEV_HI_COUNT] = {};
   DRec r{};
@@ -3933,64 +4017,133 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
   double in0[NIN] = {}, in1[NIN] = {}, v0 = 0.0, v1 = 0.0;
   float sa = 0.0f;
   const uint8_t* const own = recs + (int64_t)e * st_rb;
-  // pass 0, every env from its own record
+  // pass 0, every env from its own record (lanes past the group's envs: env e0's, unused)
   if (wave == 0) {
-    if (on) {
+    if (PV || on) {
+      // the two yaws first: the sincos waits for them alone
+      const double2* const q = (const double2*)pp;
+      const double2 o23 = *(const double2*)((const double*)(own + K.L.hd) + CBEV_HD_YAW);
+      double2 p01 = make_double2(0.0, 0.0), p23 = p01, p45 = p01;
+      double p6 = 0.0;
+      if (PV) p23 = q[1];
       load_in(own, in0);
+      in0[2] = o23.x;
+      in0[3] = o23.y;
       mb = *mp;
-      tc = K.tcount[e];
-      d_sincos(in0[2], &sh_pre[0][1][lane], &sh_pre[0][0][lane]);
+      tc = tcnt[e];
+      if (PV) {
+        ptag = *(const uint2*)&pt->row1;
+        p01 = q[0];
+        p45 = q[2];
+        p6 = pp->in[6];
+      }
+#pragma unroll 1
+      for (int it = 0; it < nround; ++it) {
+        const bool pr = pvl ? lane >= pvl : it == 1;  // this lane, this round: a preview's yaw
+        const int k = pr ? kp : lane;
+        double sn, cs;
+        d_sincos(pr ? p23.x : in0[2], &sn, &cs);
+        if (k >= 0 && k < ne_eff) {
+          sh_pre[pr][1][k] = sn;
+          sh_pre[pr][0][k] = cs;
+        }
+      }
+      if (isp) {
+        sh_pin[0][kp] = p01.x;
+        sh_pin[1][kp] = p01.y;
+        sh_pin[2][kp] = p23.x;
+        sh_pin[3][kp] = p23.y;
+        sh_pin[4][kp] = p45.x;
+        sh_pin[5][kp] = p45.y;
+        sh_pin[6][kp] = p6;
+      }
     }
   } else if (wave == 1) {
-    if (on) {
+    if (PV || on) {
       v0 = ((const double*)(own + K.L.hd))[CBEV_HD_V];
       mb = *mp;
-      tc = K.tcount[e];
+      tc = tcnt[e];
+      if (PV) ptag = *(const uint2*)&pt->row1;
+      const double pv3 = PV ? pp->in[3] : 0.0;
       float g, b;
-      d_decode_action(K, actions, e, &g, &sa, &b);  // the table lookup behind the index: on this wave alone
-      sh_act[0][lane] = g;
-      sh_act[1][lane] = sa;
-      sh_act[2][lane] = b;
-      sh_pre[0][2][lane] = hero_tan_delta(v0, sa);
+      // the table lookup behind the index: on this wave alone. A preview lane decodes its env's
+      // action again, and with PV a lane that is neither decodes env e0's: the only side effect
+      // is the error word's atomicOr of a bit the env's own lane sets anyway
+      d_decode_action(K, actions, pvl && isp ? e0 + kp : e, &g, &sa, &b);
+      if (on) {
+        sh_act[0][lane] = g;
+        sh_act[1][lane] = sa;
+        sh_act[2][lane] = b;
+      }
+#pragma unroll 1
+      for (int it = 0; it < nround; ++it) {
+        const bool pr = pvl ? lane >= pvl : it == 1;
+        const int k = pr ? kp : lane;
+        const double td = hero_tan_delta(pr ? pv3 : v0, sa);
+        if (k >= 0 && k < ne_eff) sh_pre[pr][2][k] = td;
+      }
     }
   } else {
     mb = *mp;
-    tc = K.tcount[e];
+    tc = tcnt[e];
+    if (PV) ptag = *(const uint2*)&pt->row1;
     // vis_draw <- vis of the kept envs (a reset env's comes with its bank row)
     for (int q = tid - 128; q < ne_eff * vw; q += 128) {
       const int k = q / vw, w = q - k * vw;
       uint8_t* g = recs + (int64_t)(e0 + k) * st_rb + K.L.vis;
       const uint32_t v = ((const uint32_t*)g)[w];
-      if (!(fold && K.rmask[e0 + k] != 0)) ((uint32_t*)g)[vw + w] = v;
+      if (!(fold && rmask[e0 + k] != 0)) ((uint32_t*)g)[vw + w] = v;
     }
   }
-  __syncthreads();  // cos / sin / tan and the action in LDS
+  __syncthreads();  // cos / sin / tan, the action and the previews' inputs in LDS
   CBEV_STAMP(0, 1);
   const bool reset = fold && on && mb != 0u;
   const uint64_t rbits = __ballot(reset);  // lane k = env e0 + k in every wave: the same bits, uniform branches
-  // pass 1's inputs of the reset envs, issued before the kept envs' chain runs
   const int row = reset ? bank_row_of(e, tc, K.rstride, K.rn_bank) : 0;
+  // a reset env whose preview is the preceding tail's and of this very row computes
+  // from it in the one pass, with the kept envs; any other in pass 1 (`slow`)
+  const bool fast = PV && reset && V.acc != 0u && ptag.y == V.acc && ptag.x == (uint32_t)row + 1u;
+  const bool slow = reset && !fast;
+  const uint64_t sbits = __ballot(slow);
+  // pass 1's inputs of the slow reset envs, issued before the other envs' chain runs
   const uint8_t* const bank = K.rbank + (int64_t)row * st_rb;
-  if (wave == 0 && reset) load_in(bank, in1);
-  if (wave == 1 && reset) v1 = ((const double*)(bank + K.L.hd))[CBEV_HD_V];
-  if (wave == 0 && on && !reset) chain(0, in0);
+  if (wave == 0 && slow) load_in(bank, in1);
+  if (wave == 1 && slow) v1 = ((const double*)(bank + K.L.hd))[CBEV_HD_V];
+  if (wave == 0 && on && !slow) {
+    if (fast) {
+#pragma unroll
+      for (int k = 0; k < NIN; ++k) in0[k] = sh_pin[k][lane];
+    }
+    chain(fast ? 1 : 0, in0);
+  }
   if (rbits != 0ull) {
     if (wave == 0) {
-      if (reset) {
+      if (slow) {
         // first touched here: arithmetic on them hoisted to the loads would be
-        // waited for ahead of the kept envs' chain
+        // waited for ahead of the other envs' chain
 #pragma unroll
         for (int k = 0; k < NIN; ++k) asm volatile("" : "+v"(in1[k]));
         d_sincos(in1[2], &sh_pre[1][1][lane], &sh_pre[1][0][lane]);
       }
     } else if (wave == 1) {
-      if (reset) sh_pre[1][2][lane] = hero_tan_delta(v1, sa);
+      if (slow) sh_pre[1][2][lane] = hero_tan_delta(v1, sa);
     } else {
       // the reset envs' records from their bank rows, 16-byte pieces, two per thread
-      // in flight; a piece that overlaps vis_draw word by word, its vis_draw words
-      // from the row's vis
+      // in flight; a piece that overlaps vis_draw, or the words wave 0 stores at the
+      // end (the copy leaves those out, so nothing orders the two), word by word,
+      // its vis_draw words from the row's vis
       const int np = st_rb / 16, total = __popcll(rbits) * np;
       const int d0 = (int)K.L.vis + 4 * vw, d1 = d0 + 4 * vw;
+      const int hd0 = (int)K.L.hd, hi0 = (int)K.L.hi;
+      auto head_word = [&](int o) {  // is the word at byte o of the record one of wave 0's?
+        const int d = (o - hd0) >> 3, i = (o - hi0) >> 2;
+        const bool h = o >= hd0 && ((d >= CBEV_HD_X && d < CBEV_HD_X + 8) || d == CBEV_HD_ACC ||
+                                    (d >= CBEV_HD_U_GAS && d < CBEV_HD_U_GAS + 4) || d == CBEV_HD_T);
+        return h || (o >= hi0 && i >= CBEV_HI_RS_XMIN && i <= CBEV_HI_RS_FAST);
+      };
+      auto whole = [&](int o) {  // the piece at byte o is copied as it stands
+        return (o + 16 <= d0 || o >= d1) && !(head_word(o) || head_word(o + 4) || head_word(o + 8) || head_word(o + 12));
+      };
       auto piece = [&](int q, const uint8_t** b, uint8_t** g, int* o) {  // every lane: the shuffle
         const int j = q < total ? q / np : 0, k = nth_set_bit(rbits, j);
         *o = 16 * (q - j * np);
@@ -3998,8 +4151,12 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
         *g = recs + (int64_t)(e0 + k) * st_rb + *o;
       };
       auto by_word = [&](const uint8_t* b, uint8_t* g, int o) {
-        for (int w = 0; w < 16; w += 4)
-          *(uint32_t*)(g + w) = *(const uint32_t*)(b + w - (o + w >= d0 && o + w < d1 ? 4 * vw : 0));
+        uint32_t x[4];  // the four loads in flight together: every address is inside the row
+#pragma unroll
+        for (int w = 0; w < 4; ++w) x[w] = *(const uint32_t*)(b + 4 * w - (o + 4 * w >= d0 && o + 4 * w < d1 ? 4 * vw : 0));
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+          if (!head_word(o + 4 * w)) *(uint32_t*)(g + 4 * w) = x[w];
       };
       for (int base = tid - 128; base - (tid - 128) < total; base += 256) {  // uniform trip count
         const uint8_t *b0, *b1;
@@ -4008,7 +4165,7 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
         piece(base, &b0, &g0, &o0);
         piece(base + 128, &b1, &g1, &o1);
         const bool a0 = base < total, a1 = base + 128 < total;
-        const bool w0 = o0 + 16 <= d0 || o0 >= d1, w1 = o1 + 16 <= d0 || o1 >= d1;
+        const bool w0 = whole(o0), w1 = whole(o1);
         uint4 x0 = make_uint4(0, 0, 0, 0), x1 = x0;
         if (a0 && w0) x0 = *(const uint4*)b0;
         if (a1 && w1) x1 = *(const uint4*)b1;
@@ -4018,8 +4175,10 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
         if (a1 && !w1) by_word(b1, g1, o1);
       }
     }
-    __syncthreads();  // pass 1's cos / sin / tan in LDS; the bank rows have been copied
-    if (wave == 0 && reset) chain(1, in1);
+    if (sbits != 0ull) {
+      __syncthreads();  // pass 1's cos / sin / tan in LDS
+      if (wave == 0 && slow) chain(1, in1);
+    }
   }
   CBEV_STAMP(0, 2);
   if (wave == 0 && on) {
@@ -4028,7 +4187,11 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
       // the fast bit it reads anyway: RS_FAST bits 1.. = row + 1
       hi[CBEV_HI_RS_FAST] |= (row + 1) << 1;
       if (K.stats != nullptr) K.stats[e].t0 = (double)wall_clock64();  // the episode's start
+      if (V.cnt != nullptr) atomicAdd(V.cnt + (fast ? 0 : 1), 1ull);
     }
+    // an entry this step accepts is spent, taken or not: a later step with the same
+    // tag to accept (a captured step's replays) finds none of them
+    if (PV && fold && V.acc != 0u && ptag.y == V.acc) V.pv[e].tag = 0u;
     uint8_t* g = recs + (int64_t)e * st_rb;
     double* ohd = (double*)(g + K.L.hd);
     int32_t* ohi = (int32_t*)(g + K.L.hi);
@@ -4057,6 +4220,7 @@ struct TailArgs {
   uint8_t* trunc;
   int32_t* cause;
   float* info;
+  PvArgs pv;  // the reset preview the tail writes (tag 0: none)
 };
 
 // One (env, tile) per workgroup; register target from the LDS-limited residency
@@ -4089,7 +4253,7 @@ void k_raster(RasterArgs A) {
       const TailArgs& T = M.T;
       EgoCarry C;
       ego_tail<false>(lds, M.recs, M.n, T.ne, T.rb, T.n0, T.np, T.raw_x, M.K, T.reward, T.term, T.trunc, T.cause,
-                      T.info, C);
+                      T.info, C, 0ull, &T.pv);
       return;
     }
   }
@@ -4635,6 +4799,14 @@ struct cbev_ctx {
   } pend;
   const uint8_t* last_term;   // term buffer of the last cbev_step (cbev_reset_terminated's mask)
   int last_n;                 // n of the last cbev_step (0: none yet)
+  // the reset preview (cbev_set_reset_preview, PvArgs)
+  RPreview* pv_dev;               // [CBEV_RESET_MASK_MAX_N], zeroed at creation
+  unsigned long long* pvcnt_dev;  // [2]: reset envs k_ego_head took in one pass / in two
+  int pv_on;
+  uint32_t serial;     // the last step entry's serial (never 0): the tag its tail writes
+  int pv_live;         // that entry folded a reset and wrote previews, and nothing since could change the bank or the counts
+  const void* pv_bank;  // the bank of that fold
+  int pv_n_bank;
 };
 
 // Envs per k_ego workgroup: small groups spread the record staging (LDS-DMA
@@ -4884,6 +5056,10 @@ struct StepRun {
 static int step_begin(cbev_ctx* c, int n, uint8_t* term, void* stream, StepRun* R) {
   R->s = (hipStream_t)stream;
   R->K = kargs(c);
+  // every step entry takes a serial; only cbev_step's fold makes the previews of
+  // its tail acceptable to the next entry (pv_live, set there after this)
+  if (++c->serial == 0u) c->serial = 1u;
+  c->pv_live = 0;
   c->last_term = term;
   c->last_n = n;
   if (n > c->seq_n) c->seq_n = n;
@@ -4989,6 +5165,7 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
   c->tail_ne = tail_ne_for(P, *caps, lay, ego_ne);
   c->split = c->tail_ne > 0;  // the default where supported (cbev_set_split_step)
   c->head_ne = head_ne_for();
+  c->pv_on = c->split && caps->actor_cap == 0;  // the default where the split step and the fold are (cbev_set_reset_preview)
   SgTables T;
   build_sg_tables(&T);
   hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_sg), &T, sizeof T);
@@ -5000,6 +5177,13 @@ int cbev_create(const cbev_params* params, const cbev_caps* caps, int device, cb
   const size_t seq_bytes = (size_t)CBEV_RESET_MASK_MAX_N * sizeof(uint32_t);
   if (e == hipSuccess) e = hipMalloc(&c->seq_dev, seq_bytes);
   if (e == hipSuccess) e = hipMemset(c->seq_dev, 0, seq_bytes);
+  const size_t pv_bytes = (size_t)CBEV_RESET_MASK_MAX_N * sizeof(RPreview);
+  // only where cbev_set_reset_preview can be on: the split step, records without actor slots
+  const bool pv_can = c->tail_ne > 0 && caps->actor_cap == 0;
+  if (pv_can && e == hipSuccess) e = hipMalloc(&c->pv_dev, pv_bytes);
+  if (pv_can && e == hipSuccess) e = hipMemset(c->pv_dev, 0, pv_bytes);
+  if (pv_can && e == hipSuccess) e = hipMalloc(&c->pvcnt_dev, 2 * sizeof(unsigned long long));
+  if (pv_can && e == hipSuccess) e = hipMemset(c->pvcnt_dev, 0, 2 * sizeof(unsigned long long));
   if (e == hipSuccess) {
     int khz = 0;  // wall_clock64() rate
     e = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device);
@@ -5169,6 +5353,8 @@ void cbev_destroy(cbev_ctx* c) {
   if (c->err_dev) (void)hipFree(c->err_dev);
   if (c->nterm_dev) (void)hipFree(c->nterm_dev);
   if (c->seq_dev) (void)hipFree(c->seq_dev);
+  if (c->pv_dev) (void)hipFree(c->pv_dev);
+  if (c->pvcnt_dev) (void)hipFree(c->pvcnt_dev);
   if (c->area_dev) (void)hipFree(c->area_dev);
   if (c->fov_dev) (void)hipFree(c->fov_dev);
   free(c);
@@ -5234,10 +5420,22 @@ int cbev_step(cbev_ctx* c, void* records, int n, const void* actions, uint8_t* f
   const bool fold = c->pend.on && records == c->pend.records && n == c->pend.n && off >= 0 && off % stride == 0 &&
                     off / stride < c->pend.n_frames && fold_ok(c, n);
   if (!fold) CBEV_FLUSH(c);
+  // the previews the head may take: the preceding entry's, if that folded a reset from this same bank
+  const uint32_t pvacc = fold && c->pv_on && c->split && c->pv_live && c->pv_bank == c->pend.bank && c->pv_n_bank == c->pend.n_bank
+                             ? c->serial
+                             : 0u;
+  PvArgs V{c->pv_dev, c->pvcnt_dev, 0u, 0u};
   StepRun R;
   const int rc = step_begin(c, n, term, stream, &R);
   if (rc != CBEV_OK) return rc;
   if (fold) {
+    if (c->pv_on && c->split) {
+      V.acc = pvacc;
+      V.tag = c->serial;
+      c->pv_live = 1;
+      c->pv_bank = c->pend.bank;
+      c->pv_n_bank = c->pend.n_bank;
+    }
     R.K.rmask = c->pend.mask;
     R.K.rbank = (const uint8_t*)c->pend.bank;
     R.K.rbank_frames = c->pend.bank_frames;
@@ -5255,11 +5453,12 @@ int cbev_step(cbev_ctx* c, void* records, int n, const void* actions, uint8_t* f
   if (c->split) {
     // the head, then the raster's launch with the tail as its leading workgroups
     // (a multiple of 8 of them: the XCD placement of both roles stays)
-    hipLaunchKernelGGL(k_ego_head, dim3((n + c->head_ne - 1) / c->head_ne), dim3(256), 0, R.s, (uint8_t*)records, n,
-                       c->head_ne, (int)c->L.record_bytes, R.K, actions);
+    // with previews to take, the head that loads them; otherwise the one that does not
+    hipLaunchKernelGGL(V.acc != 0u ? k_ego_head<true> : k_ego_head<false>, dim3((n + c->head_ne - 1) / c->head_ne),
+                       dim3(256), 0, R.s, (uint8_t*)records, n, c->head_ne, (int)c->L.record_bytes, R.K, actions, V);
     const EgoPack pk = ego_pack(c->L);
     T = TailArgs{((n + c->tail_ne - 1) / c->tail_ne + 7) & ~7, c->tail_ne, (int)c->L.record_bytes, pk.n0, pk.n,
-                 (int)c->L.raw_x, reward, term, trunc, cause, info};
+                 (int)c->L.raw_x, reward, term, trunc, cause, info, V};
   } else {
     launch_ego(c, k_ego, R, records, n, actions, reward, term, trunc, cause, info);
   }
@@ -5406,6 +5605,10 @@ int cbev_bank_frames(cbev_ctx* c, const void* bank, int n_bank, uint8_t* frames,
   if (!c || !bank || !frames) return set_err(CBEV_EINVAL, "null argument");
   CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
   if (!c->map_dev) return set_err(CBEV_ESTATE, "cbev_set_map not called");
+  // the rows may have new bytes: the next step takes no preview, and neither does a captured
+  // step replayed after this (the entries' tags are cleared on the stream, ahead of the render)
+  c->pv_live = 0;
+  if (c->pv_dev && c->seq_n > 0) HIP_TRY(hipMemsetAsync(c->pv_dev, 0, (size_t)c->seq_n * sizeof(RPreview), (hipStream_t)stream));
   if (n_bank <= 0) return CBEV_OK;
   KArgs K = kargs(c);
   const size_t lb = raster_lds_bytes(c->P);
@@ -5457,6 +5660,7 @@ static int launch_reset_mask(cbev_ctx* c, void* records, int n, const uint8_t* m
   const int grid = pieces >= RESET_MASK_WGS ? RESET_MASK_WGS : (int)pieces;
   const int upt = reset_mask_upt(n);
   if (n > c->seq_n) c->seq_n = n;
+  c->pv_live = 0;
   hipLaunchKernelGGL(k_reset_mask, dim3(grid), dim3(256), reset_mask_lds(n), (hipStream_t)stream, n, n_bank,
                      bank_stride(n_bank), (int)c->L.record_bytes, SS, n_frames, upt, mask, c->seq_dev,
                      (uint8_t*)records, (const uint8_t*)bank, bank_frames, frames, K);
@@ -5505,6 +5709,28 @@ int cbev_set_split_step(cbev_ctx* c, int on) {
                                 "does not fit k_raster's registers or its %zu bytes of LDS",
                    c->P.size, raster_lds_bytes(c->P));
   c->split = on != 0;
+  return CBEV_OK;
+}
+
+int cbev_set_reset_preview(cbev_ctx* c, int on) {
+  if (!c) return set_err(CBEV_EINVAL, "null argument");
+  if (on && (c->tail_ne == 0 || c->C.actor_cap != 0))
+    return set_err(CBEV_EINVAL, "the reset preview needs the split step and the folded reset: size %d, %d actor slots",
+                   c->P.size, c->C.actor_cap);
+  c->pv_on = on != 0;
+  c->pv_live = 0;
+  return CBEV_OK;
+}
+
+int cbev_reset_preview_counts(cbev_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return set_err(CBEV_EINVAL, "null argument");
+  CBEV_FLUSH(c);  // a deferred reset is applied before anything observes the state
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long v[2] = {0, 0};
+  if (c->pvcnt_dev) HIP_TRY(hipMemcpy(v, c->pvcnt_dev, sizeof v, hipMemcpyDeviceToHost));
+  out[0] = v[0];
+  out[1] = v[1];
   return CBEV_OK;
 }
 

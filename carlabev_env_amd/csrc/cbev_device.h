@@ -56,6 +56,26 @@ struct KArgs {
   uint32_t rstride;  // bank_stride(rn_bank)
 };
 
+// One env's preview: X, Y, YAW, V, ACC, TSPEED, T of bank row `row1 - 1`
+struct __attribute__((aligned(64))) RPreview {
+  double in[7];
+  uint32_t row1;  // the row + 1 (0: never written)
+  uint32_t tag;   // the step serial of the tail that wrote it (0: none, or taken)
+};
+static_assert(sizeof(RPreview) == 64, "a preview entry is one 64-byte piece");
+// The reset preview's kernel arguments (cbev_set_reset_preview). They travel in
+// k_ego_head's own arguments and in k_raster's TailArgs, not in KArgs, so every
+// other kernel keeps its kernarg layout. The tail of a step that folded a reset
+// writes, for an env it terminates, the inputs of the bank row the env's next
+// reset takes, tagged `tag` (0: writes none); the next step's k_ego_head takes
+// the entries tagged `acc` (0: takes none) whose row is the one it computes
+// itself, and counts the reset envs that did / did not in cnt[0 / 1].
+struct PvArgs {
+  RPreview* pv;             // [CBEV_RESET_MASK_MAX_N]; null where the context cannot fold a reset into a split step
+  unsigned long long* cnt;  // null with pv
+  uint32_t tag, acc;
+};
+
 // class id of padded-map texel (x, y)
 __device__ __forceinline__ int d_map_texel(const KArgs& K, int x, int y) {
   return (K.map[(int64_t)y * K.npitch + (x >> 1)] >> ((x & 1) << 2)) & 15;

@@ -195,7 +195,14 @@ int cbev_reset(cbev_ctx* ctx, void* records, int n, const void* bank, int n_bank
 
 /* Reset observations of a static scene bank, rendered once: frames = uint8[n_bank][S][S],
  * frames[b] = the observation cbev_reset would render for bank[b] (BaseMap.reset draws
- * no actors, world.py:92-100, so it depends on the bank record only). */
+ * no actors, world.py:92-100, so it depends on the bank record only).
+ * The bank-edit rule: the bytes of a bank row that a context has been given (here
+ * or in a cbev_reset_masked / cbev_reset_terminated call) may change only before
+ * a cbev_bank_frames call on that context that renders the row again. The cached
+ * frames need this anyway; the reset preview (cbev_set_reset_preview) relies on
+ * it too: a row's inputs fetched when an env terminates are used by the next
+ * step's reset unless this call came in between (it discards every fetched
+ * row on `stream`, so a captured step replayed after it sees none either). */
 int cbev_bank_frames(cbev_ctx* ctx, const void* bank, int n_bank, uint8_t* frames, void* stream);
 
 /* cbev_reset from a bank whose reset observations were rendered by cbev_bank_frames:
@@ -294,6 +301,28 @@ int cbev_flush(cbev_ctx* ctx);
  * CBEV_EINVAL (cbev_last_error says why) and the unsplit step stays. Host-side
  * state, taken when cbev_step is called; does not allocate. */
 int cbev_set_split_step(cbev_ctx* ctx, int on);
+
+/* The reset preview of the split step's folded reset. When the tail of a step
+ * that folded a reset terminates env e, it also fetches the seven inputs (X, Y,
+ * YAW, V, ACC, TSPEED, T) of the bank row e's next reset will take into a
+ * context-owned buffer (64 bytes per env, 2^20 entries = 64 MB, allocated by
+ * cbev_create where the preview can be on, nowhere else); the next step's k_ego_head then computes the reset envs in the
+ * same pass as the kept ones instead of in a second pass behind a dependent
+ * miss. A preview is taken only if the immediately preceding step entry on the
+ * context wrote it, that entry folded a reset from the same bank pointer and
+ * n_bank, no cbev_bank_frames or cbev_reset_masked / flushed reset ran in
+ * between, and its row is the one the head computes itself from the env's
+ * count; every other reset env takes the two-pass path, so a replayed captured
+ * step uses previews in its first replay only. Scheduling only: results are
+ * bit-identical either way (see the bank-edit rule at cbev_bank_frames). On by
+ * default where the split step is supported and the records have no actor
+ * slots; on = 1 elsewhere returns CBEV_EINVAL. Host-side state, taken when
+ * cbev_step is called; does not allocate. */
+int cbev_set_reset_preview(cbev_ctx* ctx, int on);
+/* out[0]: the reset envs k_ego_head computed from a preview (one pass), out[1]:
+ * those it computed from the bank row (two passes), since cbev_create.
+ * Launches a deferred reset and synchronises, like cbev_reset_counts. */
+int cbev_reset_preview_counts(cbev_ctx* ctx, uint64_t out[2]);
 
 /* Wrapper stack on the device (wrap_env, envs/__init__.py:62-83). `ring` holds
  * n_frames frames per env (uint8[n_frames][n][h][w], slot `head` the newest;
