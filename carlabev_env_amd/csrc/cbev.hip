@@ -3188,7 +3188,7 @@ constexpr int S5_PF = 4;
 // What the tail takes from S0-S4 in registers: handed over by the front in
 // k_ego, loaded by the tail itself in k_raster's tail role.
 struct EgoCarry {
-  uint64_t rbits;                 // the folded reset's envs (EgoReset::bits; 0 in the tail role: already applied)
+  uint64_t rbits;                 // the folded reset's envs (EgoReset::bits; the tail role reads its own from the records)
   uint32_t tc0;                   // thread k < ne: env e0 + k's terminations so far
   double t5x[S5_PF], t5y[S5_PF];  // S5's first route points (env tid / tpe, points sub, sub + tpe, ...)
   double pax, pay, payaw, pav;    // S5's first (env, actor) pair of this thread
@@ -3199,7 +3199,7 @@ struct EgoCarry {
 };
 // LDS of a k_ego workgroup: [ne] record slots, then (nslot == 2, contexts the
 // reset can fold into: no actor slots) [ne] bank-row slots, then the collision
-// scratch. The tail role has nslot == 1 and does not use rrow.
+// scratch. The tail role has nslot == 1: a reset env's row goes into its record slot.
 struct EgoLds {
   uint8_t* scr;  // [ne] collision scratch (from S4; the folded reset's mask bits before)
   HeroPre* pre;  // [ne]
@@ -3454,8 +3454,27 @@ constexpr uint64_t kTailHi = CBEV_HI_BIT(TIDX) | CBEV_HI_BIT(HAS_PREV_COMFORT) |
 static_assert(CBEV_HI_COUNT <= 64 && (kRasterHi & kTailHi) == 0, "the tail writes a HI word the raster reads");
 static_assert(CBEV_HI_RS_FAST == CBEV_HI_RS_R90 + CBEV_RS_WORDS && CBEV_HI_RS_R90 == CBEV_HI_RS_XMIN + 2,
               "kRasterHi: RS_XMIN .. RS_FAST are consecutive");
+//
+// An env the head reset in this step (rbits; the split step folding a reset):
+// its record is still the old episode's but for the words the head stored
+// (kHeadHi, head_word_hd), and the raster role reads that record at RS_XMIN ..
+// RS_FAST alone (kHeadHi) and everything else from the bank row (k_raster). So
+// the tail puts the whole row into the record's place here, around those HI
+// words: HD and every other HI word from the slot (the row's, with the head's
+// words over them and what the tail changed), vis from the slot, vis_draw from
+// the row's vis, and every other byte up to record_bytes from the row in HBM
+// (the route, raw_*, what follows the vis group), 16-byte pieces.
+constexpr uint64_t kHeadHi = (2ull << CBEV_HI_RS_FAST) - (1ull << CBEV_HI_RS_XMIN);
+constexpr int kHeadHiWords = CBEV_HI_RS_FAST - CBEV_HI_RS_XMIN + 1;
+constexpr int kHeadHdWords = 14;  // X .. V1, ACC, U_GAS .. U_DELTA, T
+__device__ __forceinline__ int head_word_hd(int w) {  // the w-th HD double k_ego_head stores
+  return w < 8 ? CBEV_HD_X + w : w == 8 ? CBEV_HD_ACC : w < 13 ? CBEV_HD_U_GAS + (w - 9) : CBEV_HD_T;
+}
+static_assert((kRasterHi & ~kHeadHi) == (CBEV_HI_BIT(NROUTE) | CBEV_HI_BIT(NACT) | CBEV_HI_BIT(NVEH) | CBEV_HI_BIT(NTL)) &&
+                  (kHeadHi & kTailHi) == 0,
+              "a reset env's raster reads the record at kHeadHi alone: the tail stores every other HI word there");
 __device__ __forceinline__ void ego_tail_out(const uint8_t* lds, uint8_t* __restrict__ recs, int e0, int ne,
-                                             const KArgs& K, const EgoPack& p) {
+                                             const KArgs& K, const EgoPack& p, uint64_t rbits, const int* rrow) {
   const int nhd = (int)((K.L.hi - K.L.hd) / 16), nhi = (CBEV_HI_COUNT + 3) / 4;
   const int nout = nhd + nhi + K.L.vis_words;
   const int64_t rb = K.L.record_bytes;
@@ -3468,7 +3487,9 @@ __device__ __forceinline__ void ego_tail_out(const uint8_t* lds, uint8_t* __rest
       *(uint4*)(g + o) = *(const uint4*)(l + o);
     } else if (j < nhd + nhi) {
       const int pc = j - nhd, o = (int)K.L.hi + 16 * pc;
-      const uint32_t tm = (uint32_t)(kTailHi >> (4 * pc)) & 15u, rm = (uint32_t)(kRasterHi >> (4 * pc)) & 15u;
+      const bool rk = (rbits >> k) & 1ull;  // a reset env: every word the raster does not read there
+      const uint32_t tm = (uint32_t)((rk ? ~kHeadHi : kTailHi) >> (4 * pc)) & 15u;
+      const uint32_t rm = (uint32_t)((rk ? kHeadHi : kRasterHi) >> (4 * pc)) & 15u;
       if (tm != 0u && rm == 0u) {
         *(uint4*)(g + o) = *(const uint4*)(l + o);
       } else {
@@ -3480,11 +3501,39 @@ __device__ __forceinline__ void ego_tail_out(const uint8_t* lds, uint8_t* __rest
       *(uint32_t*)(g + K.L.vis + 4 * w) = *(const uint32_t*)(l + 16 * p.n0 + (K.L.vis - K.L.raw_x) + 4 * w);
     }
   }
+  if (rbits == 0ull) return;  // uniform
+  // the rest of the reset envs' rows, HBM to HBM: [the HI pieces' end, vis) and
+  // [the vis group's end rounded up to a piece, record_bytes) as 16-byte pieces,
+  // vis_draw <- the row's vis and the words between word by word
+  const int vw = K.L.vis_words;
+  const int a0 = (int)K.L.hi + 16 * nhi, v1 = (int)K.L.vis + 8 * vw, b0 = (v1 + 15) & ~15;
+  const int na = ((int)K.L.vis - a0) / 16, nb = ((int)rb - b0) / 16, ng = (b0 - v1) / 4;
+  const int per = na + nb + vw + ng, nres = __popcll(rbits);
+  for (int q = threadIdx.x; q < nres * per; q += 256) {
+    const int i = q / per, j = q - i * per, k = nth_set_bit(rbits, i);
+    const uint8_t* b = K.rbank + (int64_t)rrow[k] * rb;
+    uint8_t* g = recs + (int64_t)(e0 + k) * rb;
+    if (j < na + nb) {
+      const int o = j < na ? a0 + 16 * j : b0 + 16 * (j - na);
+      *(uint4*)(g + o) = *(const uint4*)(b + o);
+    } else if (j < na + nb + vw) {
+      const int w = j - na - nb;
+      *(uint32_t*)(g + K.L.vis + 4 * (vw + w)) = *(const uint32_t*)(b + K.L.vis + 4 * w);
+    } else {
+      const int o = v1 + 4 * (j - na - nb - vw);
+      *(uint32_t*)(g + o) = *(const uint32_t*)(b + o);
+    }
+  }
 }
 
 // S5-S7 for the workgroup's envs. WHOLE (k_ego): after ego_front in the same
 // workgroup, on its LDS and C. Otherwise k_raster's tail role: the records are
-// the head's (a folded reset already applied: no bank slots), staged in here.
+// the head's, staged in here. Of an env the head reset (a folded reset: RS_FAST
+// bits 1.. = its bank row + 1) the record holds the head's words alone, so the
+// role stages the row into the env's own slot (no bank slots), lays the head's
+// words over it from the record, takes the route from the row and X1 / Y1 /
+// YAW1 and the pose from the record in the loads it issues ahead (pre_rec), and
+// writes the whole row into the record's place at the end (ego_tail_out).
 // GATED (k_ego_rep, substeps 2.. of cbev_step_repeat): an env whose term byte of
 // this agent step is set is frozen. Its S6 does not run (no collide_env, so no
 // episode row, no termination count, no tcount), its outputs stay as the
@@ -3513,22 +3562,45 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
   const EgoLds M = ego_lds(lds, nslot, ne, pk, SL);
   uint8_t* const scr = M.scr;
   HeroPre* const pre = M.pre;
-  const int* const rrow = M.rrow;
+  int* const rrow = M.rrow;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const cbev_params& P = K.P;
   const int64_t rb = K.L.record_bytes;
   const int A = K.C.actor_cap;
-  const uint64_t rbits = WHOLE ? C.rbits : 0ull;
+  uint64_t rbits = WHOLE ? C.rbits : 0ull;
+  if (!WHOLE && GATE == EgoGate::None && K.rmask != nullptr && K.rbank != nullptr) {
+    // The tail role of a step that folds a reset: the head has decided which envs
+    // the step resets and left the decision in their records, RS_FAST bits 1.. =
+    // bank row + 1, with the words it computed; the rest of such a record is
+    // still the old episode's. Lane k of every wave reads env e0 + k's word (the
+    // same bits in every wave: uniform branches); the rows go to LDS for src(k).
+    const int32_t* const ghi = (const int32_t*)(recs + (int64_t)(e0 + (lane < ne_eff ? lane : 0)) * st_rb + K.L.hi);
+    const int row1 = lane < ne_eff ? ghi[CBEV_HI_RS_FAST] >> 1 : 0;
+    rbits = __ballot(row1 != 0);
+    if (rbits != 0ull) {
+      if (wave == 0 && row1 != 0) rrow[lane] = row1 - 1;
+      lds_barrier();
+    }
+  }
+  // env k's source outside LDS: its record, or its bank row when the folded reset takes it
   auto src = [&](int k) -> uint8_t* {
     if (rbits != 0ull && ((rbits >> k) & 1ull))
       return (uint8_t*)K.rbank + (int64_t)rrow[k] * st_rb;
     return recs + (int64_t)(e0 + k) * st_rb;
   };
-  auto slot = [&](int k) -> uint8_t* { return lds + ((rbits >> k) & 1ull ? ne + k : k) * pk.bytes; };
+  // the tail role stages a reset env's row into the env's own slot
+  auto slot = [&](int k) -> uint8_t* { return lds + (WHOLE && ((rbits >> k) & 1ull) ? ne + k : k) * pk.bytes; };
   auto rec = [&](int k) { return bind_ego(slot(k), src(k), K, pk); };
   if (blockIdx.x == 0 && tid == 0 && K.ep_count_next != nullptr) *K.ep_count_next = 0;
   if (!WHOLE) {
+    // the loads ahead of the staging's landing: the scene from src(k), HD from the
+    // record, where the head left the poses (a kept env: the same record)
+    auto pre_rec = [&](int k) {
+      DRec g = bind_rec(src(k), K.L, K.C);
+      g.hd = (double*)(recs + (int64_t)(e0 + k) * st_rb + K.L.hd);
+      return g;
+    };
     // S0 again for the tail role: the staging (waves 2 and 3), then on waves 0
     // and 1, which issue none of it, the loads of S2 and S5's prefetches, and
     // under the staging S2 itself (the head ran the physics alone; the search
@@ -3540,7 +3612,7 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
     const int tpe2 = 128 / ne, s2k = tid / tpe2, s2sub = tid - s2k * tpe2;
     const bool s2 = wave <= 1 && s2k < ne_eff;
     S2Search<S2_PF> S2{};
-    const DRec s2g = bind_rec(src(s2 ? s2k : 0), K.L, K.C);
+    const DRec s2g = pre_rec(s2 ? s2k : 0);
     if (s2) S2.load(s2g, CBEV_HD_X1, s2sub, tpe2, K.C.route_cap);
     const int tpe5 = 256 / ne, k5 = tid / tpe5;
     if (k5 < ne_eff) ego_t5_load(C, K, bind_rec(src(k5), K.L, K.C), ne);
@@ -3553,7 +3625,7 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
     }
     C.spx = C.spy = 0.0;
     if (lane < ne_eff) {
-      const DRec g = bind_rec(src(lane), K.L, K.C);
+      const DRec g = pre_rec(lane);
       if (wave == 0) {
         ego_coll_prologue<false>(K, g, scr + lane * SL.bytes, SL, C);
       } else if (wave == 1) {
@@ -3566,6 +3638,25 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
       if (s2sub == 0) M.best[s2k] = bi;
     }
     __syncthreads();  // the staging has landed; the prologue's scratch and S2's result in LDS
+    // a reset env's slot holds its bank row: the words the head computed (head_word_*)
+    // over it, from the record
+    if (rbits != 0ull) {  // uniform
+      constexpr int per = kHeadHdWords + kHeadHiWords;
+      const int nres = __popcll(rbits);
+      for (int q = tid; q < nres * per; q += 256) {
+        const int j = q / per, w = q - j * per, k = nth_set_bit(rbits, j);
+        const uint8_t* g = recs + (int64_t)(e0 + k) * st_rb;
+        uint8_t* l = lds + k * pk.bytes;  // the first range sits at the record's offsets
+        if (w < kHeadHdWords) {
+          const int o = (int)K.L.hd + 8 * head_word_hd(w);
+          *(double*)(l + o) = *(const double*)(g + o);
+        } else {
+          const int o = (int)K.L.hi + 4 * (CBEV_HI_RS_XMIN + w - kHeadHdWords);
+          *(int32_t*)(l + o) = *(const int32_t*)(g + o);
+        }
+      }
+      __syncthreads();
+    }
     // what k_ego does between S2 and S5 and the head left out: the target index
     // update with S6's set point behind it (wave 0; lane k = S6's thread of env
     // k) beside comfort + dist2goal (wave 1), on the staged record
@@ -3724,8 +3815,6 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
   __syncthreads();
   CBEV_STAMP(1, 1);
   // S6
-  int trow1 = 0;          // the preview's row + 1 of an env this lane terminates
-  uint32_t touched = 0u;  // the row's lines, loaded for the caches alone
   if (tid < ne_eff && !(GATED && ((frozen >> tid) & 1ull))) {
     const DRec r = rec(tid);
     CollPre cp = coll_reduce_serial(scr + tid * SL.bytes, SL, r.hi[CBEV_HI_NACT], r.hi[CBEV_HI_NRAW]);
@@ -3756,36 +3845,20 @@ __device__ __forceinline__ void ego_tail(uint8_t* lds, uint8_t* __restrict__ rec
         w.u[0] = (uint32_t)row + 1u;
         w.u[1] = pvw->tag;
         o[3] = make_double2(t, w.d);
-        trow1 = row + 1;
       }
     }
   } else if (GATE == EgoGate::Mask && FIRST && tid < ne_eff) {
     reward_out[e0 + tid] = 0.0;  // an inactive env's reward of this agent step
   }
-  // The rest of such a row, for the head's record copy: wave 0 (S6's lanes are its
-  // first ne_eff) loads a word of each of the row's 128-byte lines, a line per lane,
-  // so that the next launch finds them in this XCD's L2 and their pages translated.
-  // Nothing uses the words: they are waited for at the end of the role.
-  if (!WHOLE && GATE == EgoGate::None && wave == 0 && pvw != nullptr && K.rbank != nullptr && pvw->tag != 0u) {
-    uint32_t t0 = 0u, t1 = 0u;
-    for (uint64_t tb = __ballot(trow1 != 0); tb != 0ull; tb &= tb - 1ull) {
-      const int row = __shfl(trow1, __builtin_ctzll(tb)) - 1;
-      const uint8_t* const b = K.rbank + (int64_t)row * st_rb;
-      // both loads of every lane unconditional and in flight together (a lane past the
-      // row's lines loads its last word, as every lane's second load does: the row's last
-      // line, wherever the row starts in it); a row's lines past the 64th, a loop more
-      t0 |= *(const uint32_t*)(b + min(128 * lane, st_rb - 4));
-      t1 |= *(const uint32_t*)(b + st_rb - 4);
-      for (int o = 128 * (64 + lane); o < st_rb; o += 128 * 64) t1 |= *(const uint32_t*)(b + o);
-    }
-    touched = t0 | t1;
-  }
+  // (Until the head's record copy moved into this role, wave 0 also loaded a word of
+  // each of that row's lines here, for the next head's copy to find them in L2. The
+  // row's next readers are the next step's raster and tail roles, which nothing
+  // waits for: measured with and without, DESIGN section 3, it no longer pays.)
   __syncthreads();
   CBEV_STAMP(1, 2);
   // S7
   if (!WHOLE) {
-    ego_tail_out(lds, recs, e0, ne_eff, K, pk);
-    asm volatile("" ::"v"(touched));
+    ego_tail_out(lds, recs, e0, ne_eff, K, pk, rbits, rrow);
     CBEV_STAMP(1, 3);
     return;
   }
@@ -3915,17 +3988,20 @@ __global__ __launch_bounds__(256) void k_ego_heads(uint8_t* __restrict__ recs, i
 //                    and the HI words RS_XMIN .. RS_FAST
 //   wave 1, lane k   the action decoded and tan(clip(delta)) of the same env,
 //                    beside wave 0's sincos
-//   waves 2 and 3    vis_draw <- vis, a word per thread
+//   waves 2 and 3    vis_draw <- vis of the kept envs, a word per thread
 // Every load of a pass (pose, action, vis, and the folded reset's mask byte and
 // termination count) is issued before anything waits, so a kept env pays one
 // miss latency. The folded reset (KArgs::rmask: the previous step's term bytes,
 // read here before this step's tail overwrites them): every env computes from
-// its own record without waiting for the mask. In a workgroup that holds a
-// reset env, waves 2 and 3 copy the env's bank row bank_row_of(e, tcount[e])
-// over the record (vis_draw taking the row's vis), so the tail and the raster
-// find a complete record. The copy leaves out the words wave 0 stores at the end
-// (head_word), so the two write disjoint bytes and nothing orders them: no
-// barrier stands between the copy and wave 0's stores.
+// its own record without waiting for the mask. A reset env (bank row
+// bank_row_of(e, tcount[e])) gets the same stores as a kept one, computed from
+// the row's inputs, with the decision in RS_FAST bits 1.. = row + 1, and nothing
+// else: the rest of its record stays the old episode's through this launch. The
+// next launch reads such a record at those words alone: its raster role takes
+// the scene from the bank row (k_raster), its tail role stages the row and puts
+// it into the record's place beside the raster (ego_tail, ego_tail_out). (Until
+// the copy moved there, waves 2 and 3 copied the row here, and the launch ended
+// with them: DESIGN section 3, "The folded reset without the head's copy".)
 // PV (the host launches it when the step may take previews, PvArgs::acc != 0):
 // in the first round, lane ne + k of waves 0 and 1 (the env lanes again, in a
 // second round, at ne = 64) loads env k's preview entry and computes cos / sin /
@@ -4087,7 +4163,8 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
     mb = *mp;
     tc = tcnt[e];
     if (PV) ptag = *(const uint2*)&pt->row1;
-    // vis_draw <- vis of the kept envs (a reset env's comes with its bank row)
+    // vis_draw <- vis of the kept envs (a reset env's is its bank row's vis: the raster
+    // reads it there, and the tail writes it with the rest of the row)
     for (int q = tid - 128; q < ne_eff * vw; q += 128) {
       const int k = q / vw, w = q - k * vw;
       uint8_t* g = recs + (int64_t)(e0 + k) * st_rb + K.L.vis;
@@ -4098,13 +4175,12 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
   __syncthreads();  // cos / sin / tan, the action and the previews' inputs in LDS
   CBEV_STAMP(0, 1);
   const bool reset = fold && on && mb != 0u;
-  const uint64_t rbits = __ballot(reset);  // lane k = env e0 + k in every wave: the same bits, uniform branches
   const int row = reset ? bank_row_of(e, tc, K.rstride, K.rn_bank) : 0;
   // a reset env whose preview is the preceding tail's and of this very row computes
   // from it in the one pass, with the kept envs; any other in pass 1 (`slow`)
   const bool fast = PV && reset && V.acc != 0u && ptag.y == V.acc && ptag.x == (uint32_t)row + 1u;
   const bool slow = reset && !fast;
-  const uint64_t sbits = __ballot(slow);
+  const uint64_t sbits = __ballot(slow);  // lane k = env e0 + k in every wave: the same bits, a uniform branch
   // pass 1's inputs of the slow reset envs, issued before the other envs' chain runs
   const uint8_t* const bank = K.rbank + (int64_t)row * st_rb;
   if (wave == 0 && slow) load_in(bank, in1);
@@ -4116,7 +4192,7 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
     }
     chain(fast ? 1 : 0, in0);
   }
-  if (rbits != 0ull) {
+  if (sbits != 0ull) {  // a workgroup of kept and fast lanes only runs none of this
     if (wave == 0) {
       if (slow) {
         // first touched here: arithmetic on them hoisted to the loads would be
@@ -4127,58 +4203,9 @@ __global__ __launch_bounds__(256) void k_ego_head(uint8_t* __restrict__ recs, in
       }
     } else if (wave == 1) {
       if (slow) sh_pre[1][2][lane] = hero_tan_delta(v1, sa);
-    } else {
-      // the reset envs' records from their bank rows, 16-byte pieces, two per thread
-      // in flight; a piece that overlaps vis_draw, or the words wave 0 stores at the
-      // end (the copy leaves those out, so nothing orders the two), word by word,
-      // its vis_draw words from the row's vis
-      const int np = st_rb / 16, total = __popcll(rbits) * np;
-      const int d0 = (int)K.L.vis + 4 * vw, d1 = d0 + 4 * vw;
-      const int hd0 = (int)K.L.hd, hi0 = (int)K.L.hi;
-      auto head_word = [&](int o) {  // is the word at byte o of the record one of wave 0's?
-        const int d = (o - hd0) >> 3, i = (o - hi0) >> 2;
-        const bool h = o >= hd0 && ((d >= CBEV_HD_X && d < CBEV_HD_X + 8) || d == CBEV_HD_ACC ||
-                                    (d >= CBEV_HD_U_GAS && d < CBEV_HD_U_GAS + 4) || d == CBEV_HD_T);
-        return h || (o >= hi0 && i >= CBEV_HI_RS_XMIN && i <= CBEV_HI_RS_FAST);
-      };
-      auto whole = [&](int o) {  // the piece at byte o is copied as it stands
-        return (o + 16 <= d0 || o >= d1) && !(head_word(o) || head_word(o + 4) || head_word(o + 8) || head_word(o + 12));
-      };
-      auto piece = [&](int q, const uint8_t** b, uint8_t** g, int* o) {  // every lane: the shuffle
-        const int j = q < total ? q / np : 0, k = nth_set_bit(rbits, j);
-        *o = 16 * (q - j * np);
-        *b = K.rbank + (int64_t)__shfl(row, k) * st_rb + *o;
-        *g = recs + (int64_t)(e0 + k) * st_rb + *o;
-      };
-      auto by_word = [&](const uint8_t* b, uint8_t* g, int o) {
-        uint32_t x[4];  // the four loads in flight together: every address is inside the row
-#pragma unroll
-        for (int w = 0; w < 4; ++w) x[w] = *(const uint32_t*)(b + 4 * w - (o + 4 * w >= d0 && o + 4 * w < d1 ? 4 * vw : 0));
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-          if (!head_word(o + 4 * w)) *(uint32_t*)(g + 4 * w) = x[w];
-      };
-      for (int base = tid - 128; base - (tid - 128) < total; base += 256) {  // uniform trip count
-        const uint8_t *b0, *b1;
-        uint8_t *g0, *g1;
-        int o0, o1;
-        piece(base, &b0, &g0, &o0);
-        piece(base + 128, &b1, &g1, &o1);
-        const bool a0 = base < total, a1 = base + 128 < total;
-        const bool w0 = whole(o0), w1 = whole(o1);
-        uint4 x0 = make_uint4(0, 0, 0, 0), x1 = x0;
-        if (a0 && w0) x0 = *(const uint4*)b0;
-        if (a1 && w1) x1 = *(const uint4*)b1;
-        if (a0 && w0) *(uint4*)g0 = x0;
-        if (a1 && w1) *(uint4*)g1 = x1;
-        if (a0 && !w0) by_word(b0, g0, o0);
-        if (a1 && !w1) by_word(b1, g1, o1);
-      }
     }
-    if (sbits != 0ull) {
-      __syncthreads();  // pass 1's cos / sin / tan in LDS
-      if (wave == 0 && slow) chain(1, in1);
-    }
+    __syncthreads();  // pass 1's cos / sin / tan in LDS
+    if (wave == 0 && slow) chain(1, in1);
   }
   CBEV_STAMP(0, 2);
   if (wave == 0 && on) {
@@ -4230,7 +4257,11 @@ struct TailArgs {
 // SIMD the tail would spill) run k_ego's tail on the same LDS size instead. No
 // workgroup waits for another: the head's launch has finished, the tail reads
 // nothing the raster writes, and writes nothing the raster reads
-// (ego_tail_out). ntail % 8 == 0 keeps w % 8, so the XCD placement, of both roles.
+// (ego_tail_out). That holds for an env the head reset too: its record is the
+// old episode's but for the head's words, the raster role reads it at RS_XMIN ..
+// RS_FAST alone and the scene from the bank row, which nothing writes, and the
+// tail role stores the row everywhere else in the record.
+// ntail % 8 == 0 keeps w % 8, so the XCD placement, of both roles.
 // The arguments are one struct so that the tail role can read them where it
 // uses them, through the kernarg segment's pointer: as by-value arguments every
 // field either role uses is loaded in the kernel's entry block, and the tail's
@@ -4269,13 +4300,25 @@ void k_raster(RasterArgs A) {
   const int64_t SS = (int64_t)K.P.size * K.P.size;
   const DRec r = bind_rec(recs + (int64_t)e * K.L.record_bytes, K.L, K.C);
   const RasterJob J = raster_job<false, G>(K, r);
+  // The scene of an env the head reset (this launch carries the tail and the bank:
+  // the split step folding a reset): the head wrote RS_* alone, and the tail
+  // copies the bank row over the record while this role runs, so every scene
+  // input (NROUTE / NACT / NVEH / NTL, the route, vis_draw = the row's vis, the
+  // actors and lights) is read from the row, and the record only at RS_XMIN ..
+  // RS_FAST. The raster alone (cbev_profile_raster) and the unsplit step carry no
+  // tail and read the record, complete by then.
+  const int srow = T.ntail > 0 && K.rbank != nullptr ? (r.hi[CBEV_HI_RS_FAST] >> 1) - 1 : -1;
+  DRec rs = bind_rec(srow >= 0 ? (uint8_t*)K.rbank + (int64_t)srow * K.L.record_bytes
+                               : recs + (int64_t)e * K.L.record_bytes,
+                     K.L, K.C);
+  if (srow >= 0) rs.vis_draw = rs.vis;
   // a reset k_ego folded into this step (KArgs::rmask; RS_FAST bits 1.. = its bank
   // row + 1): this tile of the bank frame into every ring slot but the one this
   // step renders (FrameStackObservation's reset padding), by the few reset
   // items only, after the render (loads and stores there: no register is held
   // across the render for it)
   const int row = K.rbank_frames != nullptr && K.rn_frames > 1 ? (r.hi[CBEV_HI_RS_FAST] >> 1) - 1 : -1;
-  raster_tile<G, true, kRasterNT>(K, r, J, t, frames + e * SS, 1, 0, lds);
+  raster_tile<G, true, kRasterNT>(K, rs, J, t, frames + e * SS, 1, 0, lds);
   if (row >= 0) raster_reset_frame<G>(K, row, e, t);
   CBEV_STAMP(2, 3);
 }
@@ -4980,8 +5023,9 @@ static void launch_raster(const cbev_ctx* c, void (*k)(A), int n, int ntail, hip
 // tail would spill: those contexts keep the unsplit k_ego.
 static int tail_ne_for(const cbev_params& P, const cbev_caps& C, const cbev_layout& L, int ego_ne) {
   if (P.size == 64) return 0;
-  const size_t per_env =
-      (size_t)ego_pack(L).bytes + coll_scratch_layout(C, L.vis_words).bytes + sizeof(HeroPre) + sizeof(int);
+  // (rrow: where a reset can fold into the split step, the reset envs' bank rows)
+  const size_t per_env = (size_t)ego_pack(L).bytes + coll_scratch_layout(C, L.vis_words).bytes + sizeof(HeroPre) +
+                         sizeof(int) + (C.actor_cap == 0 ? sizeof(int) : 0);
   for (int ne = ego_ne; ne >= 4; ne >>= 1)
     if (ne * per_env <= raster_lds_bytes(P)) return ne;
   return 0;
