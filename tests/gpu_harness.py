@@ -1,0 +1,301 @@
+"""The scaffolding the GPU tests share: a context on a map (DevWorld), the
+device episode statistics (EpisodeStatsOn), the output buffers of a step, a
+lane (one context with its bank, records, ring and outputs, make_lane), the
+loops over lanes, and the one bitwise comparison of two lanes
+(assert_same_state). Nothing here touches the GPU or the library at import.
+
+A DevWorld is destroyed in __del__ and a Lane holds it: keep a lane alive as
+long as its tensors are used.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from carlabev_env_amd import layout as LY
+from carlabev_env_amd._lib import check, lib
+
+P_ = ctypes.c_void_p
+KEYS = ("rew", "term", "trunc", "cause", "info")
+
+
+def ptr(t):
+    return P_(t.data_ptr()) if t is not None else None
+
+
+class DevWorld:
+    """A context with its map set; obs_hw: the observation size of the resize and
+    expansion kernels (cbev_set_obs_size), the context's default when None."""
+
+    def __init__(self, P, padded, caps, obs_hw=None):
+        L = lib()
+        LY.check_library_layout(L, caps)  # records are packed with the header's layout
+        self.P = P
+        self.ctx = P_()
+        check(L.cbev_create(ctypes.byref(P), ctypes.byref(caps.c()), 0, ctypes.byref(self.ctx)), "create")
+        check(L.cbev_set_map(self.ctx, padded.ctypes.data_as(P_), padded.nbytes), "set_map")
+        if obs_hw is not None:
+            check(L.cbev_set_obs_size(self.ctx, obs_hw[0], obs_hw[1]), "set_obs_size")
+
+    def __del__(self):
+        lib().cbev_destroy(self.ctx)
+
+
+class EpisodeStatsOn:
+    """The device episode statistics (cbev_set_episode_stats) on a context, as
+    the bench's info_mode "full" runs the step: k_ego then updates the per-env
+    Stats accumulators and writes a summary row per termination (the kernel
+    variant the headline measures). `check(step, term, sample, views, causes)`
+    compares this step's rows with the oracle's records of the sampled envs."""
+    RING = 4
+
+    def __init__(self, ctx, n):
+        self.n = n
+        self.stats = torch.zeros((n, LY.STATS_BYTES), dtype=torch.uint8, device="cuda")
+        self.rows = torch.zeros((self.RING, n, len(LY.EP)), dtype=torch.float64, device="cuda")
+        self.counts = torch.zeros(self.RING, dtype=torch.int32, device="cuda")
+        check(lib().cbev_set_episode_stats(ctx, ptr(self.stats), n, ptr(self.rows), ptr(self.counts), self.RING),
+              "episode_stats")
+        self.episodes = np.zeros(n, np.int64)
+        self.rows_seen = 0
+
+    def check(self, step, term_all, sample, views, causes):
+        slot = step % self.RING
+        cnt = int(self.counts[slot].item())
+        assert cnt == int(term_all.sum()), (step, cnt, int(term_all.sum()))
+        rows = self.rows[slot, :cnt].cpu().numpy()
+        by_env = {int(r[LY.EP["ENV"]]): r for r in rows}
+        assert len(by_env) == cnt, (step, "one row per terminated env")
+        for j, e in enumerate(sample):
+            v = views[j]
+            if not v.i("TERM"):
+                assert e not in by_env, (step, e)
+                continue
+            r = by_env[int(e)]
+            assert r[LY.EP["CAUSE"]] == causes[j] == v.i("CAUSE"), (step, e)
+            assert r[LY.EP["EPISODE"]] == self.episodes[e], (step, e)
+            assert r[LY.EP["LENGTH"]] == v.i("EP_LEN"), (step, e)
+            assert np.isclose(r[LY.EP["RETURN"]], v.h("EP_RETURN"), rtol=1e-9, atol=1e-12), (step, e)
+            ln = max(v.i("EP_LEN"), 1)
+            assert np.isclose(r[LY.EP["MEAN_SPEED"]], v.h("EP_SPEED") / ln, rtol=1e-9, atol=1e-12), (step, e)
+            self.rows_seen += 1
+        for e in np.flatnonzero(term_all):
+            self.episodes[e] += 1
+
+
+def error_flags(ctx):
+    f = ctypes.c_int32()
+    check(lib().cbev_error_flags(ctx, ctypes.byref(f), 1), "error_flags")
+    return f.value
+
+
+def out_bufs(n):
+    """The five output buffers of a step, by the names of KEYS."""
+    return dict(rew=torch.zeros(n, dtype=torch.float64, device="cuda"),
+                term=torch.zeros(n, dtype=torch.uint8, device="cuda"),
+                trunc=torch.zeros(n, dtype=torch.uint8, device="cuda"),
+                cause=torch.zeros(n, dtype=torch.int32, device="cuda"),
+                info=torch.zeros((n, 16), dtype=torch.float32, device="cuda"))
+
+
+# ---------------------------------------------------------------------- lanes
+class Lane(NamedTuple):
+    """One context and everything a step of it reads and writes. out: out_bufs and,
+    with the statistics on, out["stats"] (an EpisodeStatsOn)."""
+    dw: DevWorld
+    bank: torch.Tensor
+    bank_frames: torch.Tensor
+    recs: torch.Tensor
+    ring: torch.Tensor
+    out: dict
+
+
+def make_lane(P, padded, caps, recs, bank, F, *, split=None, deferred=None, preview=None, stats=True):
+    """A context on host records `recs` and bank rows `bank` (None: no bank), reset
+    into an F-slot ring. split / preview / deferred: cbev_set_split_step,
+    cbev_set_reset_preview, cbev_set_deferred_reset; one left None is not set, so
+    the context keeps the library's default. stats: the episode statistics on."""
+    L = lib()
+    S, n = P.size, len(recs)
+    dw = DevWorld(P, padded, caps)
+    if split is not None:
+        check(L.cbev_set_split_step(dw.ctx, split), "split_step")
+    if preview is not None:
+        check(L.cbev_set_reset_preview(dw.ctx, preview), "reset_preview")
+    if deferred is not None:
+        check(L.cbev_set_deferred_reset(dw.ctx, deferred), "deferred")
+    d_bank = bf = None
+    if bank is not None:
+        d_bank = torch.from_numpy(bank.copy()).cuda()
+        bf = torch.zeros((len(bank), S, S), dtype=torch.uint8, device="cuda")
+        check(L.cbev_bank_frames(dw.ctx, ptr(d_bank), len(bank), ptr(bf), None), "bank_frames")
+    d_recs = torch.from_numpy(recs.copy()).cuda()
+    ring = torch.zeros((F, n, S, S), dtype=torch.uint8, device="cuda")
+    check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), F, None), "reset")
+    out = out_bufs(n)
+    if stats:
+        out["stats"] = EpisodeStatsOn(dw.ctx, n)
+    return Lane(dw, d_bank, bf, d_recs, ring, out)
+
+
+def make_lanes(P, padded, caps, recs, bank, F, modes, stats=True):
+    """One lane per mode (a dict of make_lane's toggles) on the same records and bank."""
+    return [make_lane(P, padded, caps, recs, bank, F, stats=stats, **mode) for mode in modes]
+
+
+def step_all(lanes, acts_t, t):
+    """cbev_step of every lane with the same actions into ring slot t % F."""
+    L = lib()
+    a = torch.from_numpy(np.ascontiguousarray(acts_t)).cuda()
+    for dw, d_bank, bf, d_recs, ring, b in lanes:
+        check(L.cbev_step(dw.ctx, ptr(d_recs), len(d_recs), ptr(a), ptr(ring[t % len(ring)]), ptr(b["rew"]),
+                          ptr(b["term"]), ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), None), "step")
+    torch.cuda.synchronize()
+
+
+def reset_terminated_all(lanes):
+    L = lib()
+    for dw, d_bank, bf, d_recs, ring, b in lanes:
+        check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), len(d_recs), ptr(d_bank), len(d_bank), ptr(bf), ptr(ring),
+                                      len(ring), None), "reset_terminated")
+
+
+def flush_all(lanes):
+    for lane in lanes:
+        check(lib().cbev_flush(lane.dw.ctx), "flush")
+    torch.cuda.synchronize()
+
+
+def step_repeat(L, dw, d_recs, n, a, k, frames, b, stream=None):
+    return L.cbev_step_repeat(dw.ctx, ptr(d_recs), n, ptr(a), k, ptr(frames), ptr(b["rew"]), ptr(b["term"]),
+                              ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), stream)
+
+
+def step_masked(L, dw, d_recs, n, a, act, k, prev, frames, b, stream=None):
+    return L.cbev_step_masked(dw.ctx, ptr(d_recs), n, ptr(a), ptr(act), k, ptr(prev), ptr(frames), ptr(b["rew"]),
+                              ptr(b["term"]), ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), stream)
+
+
+def term_of(lane):
+    return lane.out["term"].cpu().numpy().astype(bool)
+
+
+def set_term(lanes, mask):
+    """The term bytes of every lane set by hand (what the next reset_terminated reads)."""
+    m = torch.from_numpy(np.asarray(mask, np.uint8)).cuda()
+    for lane in lanes:
+        lane.out["term"].copy_(m)
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------- counters
+def bank_cursor(L, dw):
+    c = ctypes.c_int64()
+    check(L.cbev_bank_cursor(dw.ctx, ctypes.byref(c)), "cursor")
+    return c.value
+
+
+def reset_counts(L, dw, n):
+    out = np.zeros(n, np.uint32)
+    check(L.cbev_reset_counts(dw.ctx, out.ctypes.data_as(P_), n), "reset_counts")
+    return out
+
+
+def termination_count(L, dw):
+    c = ctypes.c_int64()
+    check(L.cbev_termination_count(dw.ctx, ctypes.byref(c)), "termination_count")
+    return c.value
+
+
+def preview_counts(lane):
+    """(one-pass resets, two-pass resets) of a lane's context since its creation."""
+    out = (ctypes.c_uint64 * 2)()
+    check(lib().cbev_reset_preview_counts(lane.dw.ctx, out), "reset_preview_counts")
+    return int(out[0]), int(out[1])
+
+
+def reset_rows(mask_np, tcount, B):
+    """The bank rows a masked reset hands out (include/cbev.h, ABI 7): env e takes
+    (e + j * cbev_bank_stride(B)) % B, j = tcount[e], its terminations so far
+    (counted by the steps)."""
+    ids = np.flatnonzero(mask_np)
+    stride = lib().cbev_bank_stride(B)
+    rows = (ids.astype(np.int64) + tcount[ids].astype(np.int64) * stride) % B
+    return ids, rows
+
+
+# ---------------------------------------------------------------------- two lanes, the same bytes
+def same_records(a, b, layout):
+    """Records equal but for RS_FAST's bits above bit 0 (device scratch: a folded
+    reset's bank row for k_raster, k_ego -> k_raster of one step)."""
+    o = layout.off["hi"] + 4 * LY.HI["RS_FAST"]
+    a, b = a.clone(), b.clone()
+    for r in (a, b):
+        v = r.view(r.shape[0], -1)[:, o:o + 4].contiguous().view(torch.int32) & 1
+        r.view(r.shape[0], -1)[:, o:o + 4] = v.view(torch.uint8).view(r.shape[0], 4)
+    return torch.equal(a, b)
+
+
+T0 = slice(8 * 200 + 16, 8 * 200 + 24)  # cbev_episode_stats.t0 (the device clock at the episode's reset)
+
+
+def stats_difference(a, b, step, n):
+    """What differs between two contexts' episode statistics after `step`, or None:
+    the per-env accumulators (all but the reset clock stamp t0), the count of this
+    step's summary rows, or the rows (by env; all columns but the elapsed SECONDS)."""
+    sa, sb = a.stats.cpu().numpy(), b.stats.cpu().numpy()
+    keep = np.ones(sa.shape[1], bool)
+    keep[T0] = False
+    if not np.array_equal(sa[:, keep], sb[:, keep]):
+        return "accumulators"
+    slot = step % a.RING
+    ca, cb = min(int(a.counts[slot].item()), n), min(int(b.counts[slot].item()), n)
+    if ca != cb:
+        return "row count"
+    ra, rb_ = a.rows[slot, :ca].cpu().numpy(), b.rows[slot, :cb].cpu().numpy()
+    ra, rb_ = ra[np.argsort(ra[:, LY.EP["ENV"]])], rb_[np.argsort(rb_[:, LY.EP["ENV"]])]
+    cols = [c for c in range(ra.shape[1]) if c != LY.EP["SECONDS"]]
+    return None if np.array_equal(ra[:, cols], rb_[:, cols]) else "rows"
+
+
+def same_stats(a, b, step, n):
+    return stats_difference(a, b, step, n) is None
+
+
+def assert_same_outputs(a, b, t):
+    """The five outputs, the records and every ring slot of lanes a and b are equal
+    after step (or graph replay) t. All a replay can be held to: it writes its
+    episode rows into the statistics' slot of its capture."""
+    for k in KEYS:
+        assert torch.equal(a.out[k], b.out[k]), (t, k)
+    assert torch.equal(a.recs, b.recs), (t, "records", torch.nonzero((a.recs != b.recs).any(1)).flatten()[:8].tolist())
+    assert a.ring.shape == b.ring.shape, (t, "ring", a.ring.shape, b.ring.shape)
+    for f in range(len(a.ring)):
+        assert torch.equal(a.ring[f], b.ring[f]), (t, "ring", f)
+
+
+def assert_same_state(a, b, t, n, *, counts_a, counts_b, stats_ring=True):
+    """Lanes a and b (anything with .recs, .ring and .out) hold the same bytes after
+    step t: assert_same_outputs, the episode statistics (same_stats), the whole ring
+    of summary-row counts (stats_ring) and the per-env reset counts. A pure function
+    of tensors and arrays: no library call."""
+    assert_same_outputs(a, b, t)
+    sa, sb = a.out["stats"], b.out["stats"]
+    diff = stats_difference(sa, sb, t, n)
+    assert diff is None, (t, "episode stats", diff)
+    if stats_ring:
+        ca, cb = sa.counts.cpu().numpy(), sb.counts.cpu().numpy()
+        assert np.array_equal(ca, cb), (t, "counts", ca.tolist(), cb.tolist())
+    assert np.array_equal(counts_a, counts_b), (t, "reset counts")
+
+
+def assert_same(lanes, t, stats_ring=True):
+    """assert_same_state of two lanes after a step, with their cbev_reset_counts
+    (reading them applies a recorded reset: call it after the step that took it)."""
+    a, b = lanes
+    L, n = lib(), len(a.recs)
+    assert_same_state(a, b, t, n, counts_a=reset_counts(L, a.dw, n), counts_b=reset_counts(L, b.dw, n),
+                      stats_ring=stats_ring)

@@ -36,167 +36,7 @@ import numpy as np
 import oracle as O
 import episode_fixture as EF
 from carlabev_env_amd import layout as LY
-from carlabev_env_amd.config import EnvConfig
-from carlabev_env_amd.params import build_params, load_class_map, padded_map
-from carlabev_env_amd.scene_pack import pack_scene
-
-# The one table from the fixture's names to the C-ABI constants (include/cbev_layout.h
-# CBEV_CAUSE_* / CBEV_COLL_*, mirrored by layout.CAUSE / layout.COLL).
-CAUSE_CODE = {None: LY.CAUSE[None], "collision": LY.CAUSE["collision"], "success": LY.CAUSE["success"],
-              "ckpt": LY.CAUSE["ckpt"], "out_of_bounds": LY.CAUSE["out_of_bounds"],
-              "max_actions": LY.CAUSE["max_actions"], "off_road": LY.CAUSE["off_road"], "unknown": LY.CAUSE["unknown"]}
-COLL_CODE = {None: LY.COLL[None], "vehicle": LY.COLL["vehicle"], "pedestrian": LY.COLL["pedestrian"],
-             "target": LY.COLL["target"]}
-ACTOR_ID_NONE, ACTOR_ID_GOAL = -1, -2  # HI ACTOR_ID: -1 None, -2 "goal", else the reference's int id
-
-# (abs, rel): 10 x the measured deviations (module docstring), capped by the piecewise bounds
-MEASURED = {"hero": (1.110e-16, 2.203e-16), "actors": (1.297e-13, 1.538e-13), "reward": (1.041e-15, 8.862e-16)}
-CAP = {"hero": (1e-9, 1e-11), "actors": (1e-7, 1e-9), "reward": (1e-9, 1e-11)}
-BOUND = {k: (min(10 * MEASURED[k][0], CAP[k][0]), min(10 * MEASURED[k][1], CAP[k][1])) for k in MEASURED}
-
-
-def world_of(config):
-    """(P, padded map) of a fixture configuration."""
-    cont = config["action_profile"].startswith("continuous")
-    carl = config["reward_profile"].startswith("carl")
-    size = config["size"]
-    cfg = EnvConfig(size=size, obs_size=(size, size), render_mode="rgb_array", action_mode="continuous" if cont else "discrete",
-                    action_profile_id=config["action_profile"], reward_mode="carl" if carl else "shaping",
-                    reward_profile_id=config["reward_profile"], ego_anchor_y_frac=config["anchor_y"], obs_mode="bev_semantic")
-    classes = load_class_map(cfg.map_name, size)
-    P = build_params(cfg, classes)
-    P.max_actions = int(config["max_actions"])
-    padded, pitch = padded_map(classes, P.pad)
-    assert pitch == P.map_pitch
-    return P, padded
-
-
-def pack_episode(ep, caps=None):
-    """(record, layout, caps): the episode's scene packed into a zeroed record."""
-    spec = ep.scene_spec()
-    if caps is None:
-        caps = LY.Caps(*spec.caps_needed())
-    layout = LY.Layout.make(caps)
-    rec = np.zeros(layout.record_bytes, np.uint8)
-    view = LY.RecordView(rec, layout)
-    pack_scene(view, spec, ep.config["size"], scene_id=ep.index)
-    # the scene scalars episode_info reports (carlabev.py:180-181; host_reset sets them after packing)
-    view.hd[LY.HD["NUM_VEH"]] = float(len(spec.vehicles))
-    view.hd[LY.HD["LEN_ROUTE_M"]] = float(ep.meta["len_ego_route"])
-    return rec, layout, caps
-
-
-class Deviation:
-    """Compares float64 values with the fixture and keeps the largest deviations
-    seen per class of value: abs where |want| < 1, rel elsewhere. libm: the
-    relative bar added for device libm (the GPU test); it applies at the scale of
-    the operands, which is at least 1 (positions, angles), so values below 1 in
-    magnitude take it as an absolute term, as the parity suite's atol does.
-    actor_yaw_mod: actor headings are compared modulo 2 pi (the GPU test; see
-    test_gpu_parity.angles_close for why a retreat's rebuilt route needs it)."""
-
-    def __init__(self, libm=0.0, actor_yaw_mod=False):
-        self.seen = {k: [0.0, 0.0] for k in MEASURED}
-        self.libm, self.actor_yaw_mod = libm, actor_yaw_mod
-
-    def check(self, kind, got, want, tag):
-        got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-        assert got.shape == want.shape, (tag, got.shape, want.shape)
-        d = np.abs(got - want)
-        small = np.abs(want) < 1.0
-        a = float(np.max(d[small], initial=0.0))
-        r = float(np.max(d[~small] / np.abs(want[~small]), initial=0.0))
-        self.seen[kind][0] = max(self.seen[kind][0], a)
-        self.seen[kind][1] = max(self.seen[kind][1], r)
-        atol, rtol = BOUND[kind]
-        assert a <= atol + self.libm and r <= rtol + self.libm, (tag, kind, "abs", a, "rel", r, got, want)
-
-
-def vis_bits(view, n):
-    return np.array([(int(view.vis[i >> 5]) >> (i & 31)) & 1 for i in range(n)], np.uint8)
-
-
-def want_actor_id(ep, t):
-    kind = ep._fx.meta["actor_id_kinds"][int(ep.actor_id_kind[t])]
-    return {"none": ACTOR_ID_NONE, "goal": ACTOR_ID_GOAL}.get(kind, int(ep.actor_id[t]))
-
-
-def compare_reset(ep, view, dev, tile):
-    """tile: the class under the hero at reset, or None where the record does not
-    hold it yet (the device writes TILE from the first step on)."""
-    dev.check("hero", view.hd[LY.HD["X"]:LY.HD["X"] + 4], ep.reset_hero, (ep.name, "reset hero"))
-    assert view.i("TIDX") == ep.reset_tidx and view.i("NROUTE") == ep.n_route, (ep.name, "reset route")
-    dev.check("hero", [view.h("D2G"), view.h("D2G_T1")], [ep.reset_d2g] * 2, (ep.name, "reset dist2goal"))
-    assert tile is None or tile == ep.reset_tile, (ep.name, "reset tile")
-    assert view.i("NACT") == ep.n_actors
-    assert np.array_equal(vis_bits(view, ep.n_route), ep.visible[0]) and ep.visible[0].all(), (ep.name, "reset targets")
-    compare_actors(ep, view, 0, dev)
-
-
-def compare_actors(ep, view, row, dev):
-    n = ep.n_actors
-    if n == 0:
-        return
-    tag = (ep.name, row - 1, "actors")
-    assert np.array_equal(view.ai[LY.AI["KIND"], :n] - 1, ep.sa_kind), tag
-    assert np.array_equal(view.ai[LY.AI["SIZE"], :n], ep.sa_size), tag
-    got = view.ad[LY.AD["X"]:LY.AD["X"] + 4, :n].T.copy()
-    if dev.actor_yaw_mod:  # bring the heading to the recorded one's turn
-        got[:, 2] -= 2 * np.pi * np.rint((got[:, 2] - ep.act_state[row, :, 2]) / (2 * np.pi))
-    dev.check("actors", got, ep.act_state[row], tag)
-    assert np.array_equal(view.ai[LY.AI["TIDX"], :n], ep.act_tidx[row]), tag + ("tidx",)
-    names = ep._fx.meta["bstate_names"]
-    want = [LY.BSTATE[names[int(b)]] for b in ep.act_bstate[row]]
-    assert np.array_equal(view.ai[LY.AI["BSTATE"], :n], want), tag + ("behaviour state",)
-    assert np.array_equal(view.ai[LY.AI["BRAKING"], :n], ep.act_braking[row]), tag + ("braking",)
-
-
-def listed_actors(ep, t, rows):
-    """The actors the reference listed in actors_state on step t: each row's position
-    is one recorded actor's, and the list keeps the actor order."""
-    listed = []
-    for r in rows:
-        hit = [a for a in range(ep.n_actors) if a not in listed and r[0] == ep.act_state[t + 1, a, 0]
-               and r[1] == ep.act_state[t + 1, a, 1]]
-        assert hit, (ep.name, t, "an actors_state row that is no recorded actor")
-        listed.append(hit[0])
-    assert listed == sorted(listed), (ep.name, t, "actors_state out of actor order")
-    types = ep.actors_state_type[int(ep.as_off[t]):int(ep.as_off[t + 1])]
-    assert np.array_equal(types, ep.sa_kind[listed]), (ep.name, t, "actors_state types")
-    return listed
-
-
-def compare_step(ep, t, view, cause, dev):
-    """Everything recorded after step t against a record (the oracle's or the device's)."""
-    M = ep._fx.meta
-    tag = (ep.name, t)
-    hd = view.hd
-    dev.check("hero", hd[LY.HD["X"]:LY.HD["X"] + 4], ep.hero[t], tag + ("state",))
-    dev.check("hero", hd[LY.HD["X1"]:LY.HD["X1"] + 4], ep.hero_last[t], tag + ("last_state",))
-    dev.check("hero", [view.h("DIST2WP"), view.h("D2G"), view.h("D2G_T1")], [ep.dist2wp[t], ep.d2g[t], ep.d2g_t1[t]],
-              tag + ("dist2wp, dist2goal, dist2goal_t_1",))
-    assert view.i("TIDX") == ep.tidx[t], tag + ("target index",)
-    assert view.i("TILE") == ep.tile[t], tag + ("tile",)
-    assert view.i("COLLIDED") == COLL_CODE[M["coll_names"][int(ep.collided[t])]], tag + ("collided",)
-    assert view.i("ACTOR_ID") == want_actor_id(ep, t), tag + ("actor_id", view.i("ACTOR_ID"))
-    assert view.i("NACTSTATE") == ep.n_actors_state[t], tag + ("len(actors_state)",)
-    assert np.array_equal(vis_bits(view, ep.n_route), ep.visible[t + 1]), tag + ("target visibility",)
-    compare_actors(ep, view, t + 1, dev)
-    # the rows of actors_state are (x, y, v cos yaw, v sin yaw) of the listed actors, in actor order: the record keeps
-    # their count, the actors above pin their values, and the reward below what the reward functions made of them
-    rows = ep.actors_state_rows(t)
-    assert len(rows) == ep.n_actors_state[t], tag + ("actors_state rows",)
-    if len(rows):
-        listed = listed_actors(ep, t, rows)
-        x, y, yaw, v = (view.ad[LY.AD[k], listed] for k in ("X", "Y", "YAW", "V"))
-        dev.check("actors", np.stack([x, y, v * np.cos(yaw), v * np.sin(yaw)], axis=1), rows, tag + ("actors_state rows",))
-    dev.check("reward", [view.h("REWARD")], [ep.reward[t]], tag + ("reward",))
-    dev.check("reward", hd[LY.HD["C_SPEED"]:LY.HD["C_SPEED"] + 7], ep.comfort[t], tag + ("comfort",))
-    dev.check("reward", hd[LY.HD["U_GAS"]:LY.HD["U_GAS"] + 4], ep.control[t], tag + ("control",))
-    assert cause == CAUSE_CODE[M["cause_names"][int(ep.cause[t])]], tag + ("cause", cause)
-    assert view.i("CAUSE") == CAUSE_CODE[M["cause_names"][int(ep.sticky[t])]], tag + ("sticky cause",)
-    assert view.i("TERM") == ep.terminated[t] and view.i("TRUNC") == ep.truncated[t], tag + ("terminated, truncated",)
-    assert view.i("STEP") == ep.current_step[t] == view.i("EP_LEN"), tag + ("_current_step",)
+from episode_fixture import Deviation, compare_reset, compare_step, compare_summary, pack_episode, world_of
 
 
 def summary_of(view):
@@ -209,13 +49,6 @@ def summary_of(view):
             "mean_abs_yaw_rate": h("EP_ABS_YR") / n, "mean_abs_yaw_acc": h("EP_ABS_YACC") / n,
             "comfort_violation_rate": h("EP_VIOL") / n, "harsh_brake_rate": h("EP_HARSH") / n,
             "num_vehicles": h("NUM_VEH")}
-
-
-def compare_summary(ep, got, cause, dev):
-    M = ep._fx.meta
-    keys = [k for k in M["summary_keys"] if k in got]
-    dev.check("reward", [got[k] for k in keys], [ep.summary[k] for k in keys], (ep.name, "episode_info", keys))
-    assert cause == CAUSE_CODE[M["cause_names"][ep.termination]], (ep.name, "episode_info termination")
 
 
 def replay(ep, dev):

@@ -17,10 +17,10 @@ torch = pytest.importorskip("torch")
 import oracle as O
 from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import check, lib
+from gpu_harness import (P_, DevWorld, EpisodeStatsOn, assert_same, assert_same_outputs, error_flags, flush_all,
+                         make_lanes, out_bufs, ptr, reset_counts, reset_terminated_all, step_repeat, term_of)
+from gpu_scenes import compare_records, deferred_pair, edge_states, info_of, split_pair
 from helpers import CAPS_FULL, action_stream, bench_caps, build_records, world
-from test_gpu_parity import (DevWorld, EpisodeStatsOn, P_, _authored64, _counts, _deferred_pair, _edge_states,
-                             _same_stats, compare_records, error_flags, info_of, ptr)
-from test_gpu_split_step import _bufs, _split_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -42,11 +42,6 @@ def oracle_agent_step(orc, recs, layout, acts_t, frames, k):
             if v.i("TERM"):
                 break
     return rsum, cause, last
-
-
-def step_repeat(L, dw, d_recs, n, a, k, frames, b, stream=None):
-    return L.cbev_step_repeat(dw.ctx, ptr(d_recs), n, ptr(a), k, ptr(frames), ptr(b["rew"]), ptr(b["term"]),
-                              ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), stream)
 
 
 def run_repeat_parity(kinds, n, agent_steps, k, size=128, reward="carl_base_v1", seed0=0, act_seed=1234, caps=None,
@@ -77,7 +72,7 @@ def run_repeat_parity(kinds, n, agent_steps, k, size=128, reward="carl_base_v1",
     if acts is None:
         acts = action_stream(P, n, agent_steps, seed=act_seed)
     st = EpisodeStatsOn(dw.ctx, n)
-    b = _bufs(n)
+    b = out_bufs(n)
     hist = np.zeros(k + 1, np.int64)
     views = [LY.RecordView(recs[e], layout) for e in range(n)]
     for t in range(agent_steps):
@@ -151,7 +146,7 @@ def test_truncation_inside_a_repeat():
 
     def edit(recs, layout, P):
         x1 = LY.RecordView(recs[1], layout).hd[LY.HD["X"]]
-        _edge_states(recs, layout, P)
+        edge_states(recs, layout, P)
         # _edge_states moves env 1 off the road, where it collides in substep 1 and
         # would never reach its truncation: env 1 keeps its own pose here
         LY.RecordView(recs[1], layout).hd[LY.HD["X"]] = x1
@@ -181,30 +176,19 @@ def test_repeat_at_size_64():
                       world_=(P, padded), acts=np.ascontiguousarray(acts[:, idx]))
 
 
-def _same_everything(L, A, B, t, n):
-    (dA, _, _, rA, gA, bA), (dB, _, _, rB, gB, bB) = A, B
-    for key in ("rew", "term", "trunc", "cause", "info"):
-        assert torch.equal(bA[key], bB[key]), (t, key)
-    assert torch.equal(rA, rB), (t, "records")
-    assert torch.equal(gA, gB), (t, "ring")
-    assert _same_stats(bA["stats"], bB["stats"], t, n), (t, "episode stats")
-    assert np.array_equal(bA["stats"].counts.cpu().numpy(), bB["stats"].counts.cpu().numpy()), (t, "counts")
-    assert np.array_equal(_counts(L, dA, n), _counts(L, dB, n)), (t, "reset counts")
-
-
 def test_repeat_1_is_the_plain_step_bitwise():
     """cbev_step_repeat(repeat=1) forwards to cbev_step: the folded reset included."""
     n, n_bank, F, steps = 19, 53, 3, 20
-    P, ctxs = _split_pair(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_319, 14_319, n_bank=n_bank, F=F)
+    P, lanes = split_pair(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_319, 14_319, n_bank=n_bank, F=F)
     L = lib()
-    for dw, *_ in ctxs:
-        check(L.cbev_set_split_step(dw.ctx, 0), "split off")
+    for lane in lanes:
+        check(L.cbev_set_split_step(lane.dw.ctx, 0), "split off")
     acts = action_stream(P, n, steps, seed=5)
-    A, B = ctxs
+    A, B = lanes
     folded = 0
     for t in range(steps):
         a = torch.from_numpy(np.ascontiguousarray(acts[t])).cuda()
-        folded += L.cbev_reset_pending(B[0].ctx)
+        folded += L.cbev_reset_pending(B.dw.ctx)
         dw, _, _, d_recs, ring, b = A
         check(L.cbev_step(dw.ctx, ptr(d_recs), n, ptr(a), ptr(ring[t % F]), ptr(b["rew"]), ptr(b["term"]),
                           ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), None), "step")
@@ -212,15 +196,11 @@ def test_repeat_1_is_the_plain_step_bitwise():
         check(step_repeat(L, dw, d_recs, n, a, 1, ring[t % F], b), "step_repeat")
         assert L.cbev_reset_pending(dw.ctx) == 0  # taken by the step, as cbev_step takes it
         torch.cuda.synchronize()
-        _same_everything(L, A, B, t, n)
-        for dw, d_bank, bf, d_recs, ring, b in ctxs:
-            check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n, ptr(d_bank), n_bank, ptr(bf), ptr(ring), F, None),
-                  "reset_terminated")
-    for dw, *_ in ctxs:
-        check(L.cbev_flush(dw.ctx), "flush")
-    torch.cuda.synchronize()
-    assert torch.equal(A[3], B[3]) and torch.equal(A[4], B[4])
-    assert folded >= steps - 1 and int(_counts(L, A[0], n).sum()) > 0
+        assert_same(lanes, t)
+        reset_terminated_all(lanes)
+    flush_all(lanes)
+    assert torch.equal(A.recs, B.recs) and torch.equal(A.ring, B.ring)
+    assert folded >= steps - 1 and int(reset_counts(L, A.dw, n).sum()) > 0
 
 
 def test_repeat_equals_chained_plain_steps_bitwise():
@@ -234,15 +214,8 @@ def test_repeat_equals_chained_plain_steps_bitwise():
     recs, _ = build_records(builder, n, ["rt_no_traffic_v1"], seed0=10_000)
     acts = action_stream(P, n, steps, seed=1234)
     L = lib()
-    S = P.size
-    ctxs = []
-    for _ in range(2):
-        dw = DevWorld(P, padded, caps)
-        d_recs = torch.from_numpy(recs.copy()).cuda()
-        fr = torch.zeros((n, S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(fr), 1, None), "reset")
-        ctxs.append((dw, d_recs, fr, _bufs(n)))
-    (dA, rA, fA, bA), (dB, rB, fB, bB) = ctxs
+    (dA, _, _, rA, gA, bA), (dB, _, _, rB, gB, bB) = make_lanes(P, padded, caps, recs, None, 1, [{}, {}], stats=False)
+    fA, fB = gA[0], gB[0]
     same = 0
     for t in range(steps):
         a = torch.from_numpy(np.ascontiguousarray(acts[t])).cuda()
@@ -272,9 +245,9 @@ def test_canonical_loop_deferred_equals_immediate():
     (the repeat step launches the recorded reset before substep 1) against the
     same with it off: everything equal after every agent step."""
     n, B, F, k, steps = 45, 13, 3, 3, 25
-    P, layout, ctxs = _deferred_pair(n, B, F, bench_caps(2), 7000, 17000)
+    P, layout, lanes = deferred_pair(n, B, F, bench_caps(2), 7000, 17000)
     L = lib()
-    for dw, d_bank, bf, d_recs, ring, b in ctxs:  # every third bank row starts off the road
+    for dw, d_bank, bf, d_recs, ring, b in lanes:  # every third bank row starts off the road
         check(L.cbev_flush(dw.ctx), "flush")
         h = d_bank.cpu().numpy()
         for r in range(0, B, 3):
@@ -286,27 +259,23 @@ def test_canonical_loop_deferred_equals_immediate():
             LY.RecordView(h[e], layout).hd[LY.HD["X"]] += 60.0
         d_recs.copy_(torch.from_numpy(h))
     acts = action_stream(P, n, steps, seed=21)
-    A, Bc = ctxs
+    A, Bc = lanes
     was_reset = np.zeros(n, bool)
     reset_then_term = pending = 0
     for t in range(steps):
         a = torch.from_numpy(np.ascontiguousarray(acts[t])).cuda()
-        pending += L.cbev_reset_pending(Bc[0].ctx)
-        for dw, d_bank, bf, d_recs, ring, b in ctxs:
+        pending += L.cbev_reset_pending(Bc.dw.ctx)
+        for dw, d_bank, bf, d_recs, ring, b in lanes:
             check(step_repeat(L, dw, d_recs, n, a, k, ring[t % F], b), "step_repeat")
             assert L.cbev_reset_pending(dw.ctx) == 0
         torch.cuda.synchronize()
-        _same_everything(L, A, Bc, t, n)
-        tn = Bc[5]["term"].cpu().numpy().astype(bool)
+        assert_same(lanes, t)
+        tn = term_of(Bc)
         reset_then_term += int(np.sum(was_reset & tn))
         was_reset = tn
-        for dw, d_bank, bf, d_recs, ring, b in ctxs:
-            check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n, ptr(d_bank), B, ptr(bf), ptr(ring), F, None),
-                  "reset_terminated")
-    for dw, *_ in ctxs:
-        check(L.cbev_flush(dw.ctx), "flush")
-    torch.cuda.synchronize()
-    assert torch.equal(A[3], Bc[3]) and torch.equal(A[4], Bc[4])
+        reset_terminated_all(lanes)
+    flush_all(lanes)
+    assert torch.equal(A.recs, Bc.recs) and torch.equal(A.ring, Bc.ring)
     assert pending >= steps - 1 and reset_then_term > 0
 
 
@@ -316,25 +285,14 @@ def _repeat_world(n, F, seed0, push_every):
     recs, _ = build_records(builder, n, ["rt_no_traffic_v1"], seed0=seed0)
     for e in range(0, n, push_every):
         LY.RecordView(recs[e], layout).hd[LY.HD["X"]] += 60.0
-    L = lib()
-    S = P.size
-    ctxs = []
-    for _ in range(2):
-        dw = DevWorld(P, padded, caps)
-        d_recs = torch.from_numpy(recs.copy()).cuda()
-        ring = torch.zeros((F, n, S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), F, None), "reset")
-        b = _bufs(n)
-        b["stats"] = EpisodeStatsOn(dw.ctx, n)
-        ctxs.append((dw, d_recs, ring, b))
-    return P, layout, ctxs
+    return P, layout, make_lanes(P, padded, caps, recs, None, F, [{}, {}])
 
 
 def test_repeat_under_graph_capture():
     """One repeat step (k = 3) captured into a graph (a linear chain, nothing
     allocated) and replayed twice equals two eager calls from the same start."""
     n, F, k = 19, 2, 3
-    P, layout, ctxs = _repeat_world(n, F, 10_500, 4)
+    P, layout, lanes = _repeat_world(n, F, 10_500, 4)
     L = lib()
     acts = torch.ones(n, dtype=torch.int32, device="cuda")
 
@@ -342,10 +300,10 @@ def test_repeat_under_graph_capture():
         check(step_repeat(L, dw, d_recs, n, acts, k, ring[0], b, P_(torch.cuda.current_stream().cuda_stream)),
               "step_repeat")
 
-    for c in ctxs:  # one eager call each: the kernels are loaded before the capture
-        step(*c)
+    (dA, _, _, rA, gA, bA), (dB, _, _, rB, gB, bB) = lanes
+    step(dA, rA, gA, bA)  # one eager call each: the kernels are loaded before the capture
+    step(dB, rB, gB, bB)
     torch.cuda.synchronize()
-    (dA, rA, gA, bA), (dB, rB, gB, bB) = ctxs
     side = torch.cuda.Stream()
     g = torch.cuda.CUDAGraph()
     side.wait_stream(torch.cuda.current_stream())
@@ -358,18 +316,15 @@ def test_repeat_under_graph_capture():
         step(dA, rA, gA, bA)
         g.replay()
         torch.cuda.synchronize()
-        for key in ("rew", "term", "trunc", "cause", "info"):
-            assert torch.equal(bA[key], bB[key]), (rep, key)
-        assert torch.equal(rA, rB), (rep, "records")
-        assert torch.equal(gA, gB), (rep, "ring")
+        assert_same_outputs(*lanes, rep)
     assert int(bA["term"].sum()) > 0
 
 
 def test_refusals_leave_a_live_context_untouched():
     n, F = 19, 2
-    P, layout, ctxs = _repeat_world(n, F, 10_600, 4)
+    P, layout, lanes = _repeat_world(n, F, 10_600, 4)
     L = lib()
-    dw, d_recs, ring, b = ctxs[0]
+    dw, _, _, d_recs, ring, b = lanes[0]
     acts = torch.ones(n, dtype=torch.int32, device="cuda")
     check(step_repeat(L, dw, d_recs, n, acts, 2, ring[0], b), "step_repeat")
     torch.cuda.synchronize()

@@ -14,11 +14,9 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from carlabev_env_amd._lib import lib
+from gpu_harness import P_, ptr
+from gpu_scenes import EGO_ONLY, ego_only_64, eval_actions, eval_cfg, obs_world, relaid
 from helpers import CAPS_FULL, bench_caps
-from test_gpu_masked_step import EGO_ONLY, _eval_actions, _eval_cfg, ego_only_64
-from test_gpu_obs_dtype import Ctx
-from test_gpu_parity import P_, ptr
-from test_gpu_stack_heads import relaid
 
 pytestmark = pytest.mark.gpu
 
@@ -110,7 +108,7 @@ GEOMETRIES = [
 
 @pytest.mark.parametrize("hw,F,ring_off,sizes", GEOMETRIES)
 def test_final_frames_equals_torch_indexing(hw, F, ring_off, sizes):
-    c = Ctx(hw)
+    c = obs_world(hw)
     for n in sizes:
         for mask_off in (0, 1):  # 1: the ranking's byte path
             b = Bufs(hw, n, F, ring_off, mask_off, seed=1000 * n + F)
@@ -129,7 +127,7 @@ def test_final_frames_equals_torch_indexing(hw, F, ring_off, sizes):
 
 def test_refusals_write_nothing():
     hw, n, F = (96, 96), 17, 3
-    c = Ctx(hw)
+    c = obs_world(hw)
     b = Bufs(hw, n, F)
     b.mask.fill_(1)
     L = lib()
@@ -178,7 +176,7 @@ def test_final_frames_under_graph_capture():
     """Captured once on a side stream, replayed twice with the mask edited in
     between: each replay ranks the mask as it is then."""
     hw, n, F = (96, 96), 257, 3
-    c = Ctx(hw)
+    c = obs_world(hw)
     b = Bufs(hw, n, F, seed=5)
     heads = torch.from_numpy(np.random.default_rng(2).integers(0, F, n).astype(np.uint8)).cuda()
     masks = [torch.from_numpy(m).cuda() for m in (_masks(n, 31)["random"], _masks(n, 32)["bytes-2-0xff"],
@@ -216,7 +214,7 @@ def _make(monkeypatch, autoreset, cfg_update=None, caps=EGO_ONLY, difficulty="rt
     test_gpu_masked_step's nine authored ones, env e running scene e % 9, and
     they are the bank as well."""
     from carlabev_env_amd import RandomNavigationReset, build_random_navigation_options, make_env
-    cfg = _eval_cfg(monkeypatch, MAX_ACTIONS)
+    cfg = eval_cfg(monkeypatch, MAX_ACTIONS)
     if cfg_update:
         cfg = type(cfg)(**{**cfg.model_dump(), **cfg_update})
     env = make_env({"env": cfg, "num_envs": n}, num_envs=n, caps=caps, autoreset=autoreset, **kw)
@@ -272,7 +270,7 @@ def test_same_step_equals_step_then_reset_terminated(monkeypatch, cfg_update, kw
     ar = torch.arange(N, device="cuda")
 
     def both(t):
-        a = _eval_actions(N, t)
+        a = eval_actions(N, t)
         oa, ra, ta, ua, ia = A.step(a)
         fin, ids = A.final_obs()
         ob, rb, tb, ub, ib = B.step(a)
@@ -326,7 +324,7 @@ def test_same_step_with_an_active_mask(monkeypatch, stack_heads):
     off = ~active
     t = 0
     while True:  # every env is truncated by the same step (max_actions), if not earlier
-        _, _, term, _, _ = A.step(_eval_actions(N, t), active=everyone)
+        _, _, term, _, _ = A.step(eval_actions(N, t), active=everyone)
         t += 1
         assert t <= MAX_ACTIONS
         if bool(term[off].any()):
@@ -337,7 +335,7 @@ def test_same_step_with_an_active_mask(monkeypatch, stack_heads):
     counts0, recs0, ring0 = A.reset_counts(), A.records.clone(), A.ring.clone()
     seen_active_end = False
     for _ in range(MAX_ACTIONS + 1):
-        obs, rew, term, _, _ = A.step(_eval_actions(N, t), active=active)
+        obs, rew, term, _, _ = A.step(eval_actions(N, t), active=active)
         t += 1
         fin, ids = A.final_obs()
         assert bool(term[just_ended].all()), "the stale term bytes the mask has to be and-combined against"
@@ -368,7 +366,7 @@ def test_surface(monkeypatch):
     assert "metadata" not in vars(D)
     assert not hasattr(D, "_final") and not hasattr(D, "_final_env") and not hasattr(D, "_final_count")
     assert A._final.shape == A._ring.shape and A._final_env.shape == (4,) and A._final_count.shape == (1,)
-    a = _eval_actions(4, 0)
+    a = eval_actions(4, 0)
     with pytest.raises(RuntimeError, match="before any step"):
         A.final_obs()
     with pytest.raises(RuntimeError, match="same_step"):
@@ -403,7 +401,7 @@ def test_same_step_on_the_bare_rgb_observation(monkeypatch):
     B = _make(monkeypatch, "disabled", n=n, wrappers=False)
     ended = 0
     for t in range(MAX_ACTIONS + 1):
-        a = _eval_actions(n, t)
+        a = eval_actions(n, t)
         oa, _, ta, _, _ = A.step(a)
         fin, ids = A.final_obs()
         ob, _, tb, _, _ = B.step(a)
@@ -414,7 +412,7 @@ def test_same_step_on_the_bare_rgb_observation(monkeypatch):
     assert ended >= n
     for env in (A, B):
         env.close()
-    cfg = _eval_cfg(monkeypatch, MAX_ACTIONS)
+    cfg = eval_cfg(monkeypatch, MAX_ACTIONS)
     cfg = type(cfg)(**{**cfg.model_dump(), "obs_mode": "vector"})
     with pytest.raises(ValueError, match="autoreset.*vector"):
         make_env({"env": cfg, "num_envs": 2}, num_envs=2, caps=EGO_ONLY, wrappers=False, autoreset="same_step")

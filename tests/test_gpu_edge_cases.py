@@ -19,8 +19,9 @@ torch = pytest.importorskip("torch")
 
 import edge_cases as EC
 from carlabev_env_amd import layout as LY
-from carlabev_env_amd._lib import check, lib
-from test_gpu_parity import DevWorld, _cached_bank_frames_match_render, error_flags, ptr, run_parity
+from carlabev_env_amd._lib import lib
+from gpu_harness import error_flags, make_lanes, step_all
+from gpu_scenes import cached_bank_frames_match_render, run_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -69,7 +70,7 @@ def test_reduced_crop_bank_frames_match_render(geo):
     in tile_out_check) where every reset frame takes the checked path, against
     each other and against the oracle's reset frames."""
     P, padded, caps, recs, layout, _ = _reduced_batch(geo)
-    _cached_bank_frames_match_render(P, padded, caps, np.ascontiguousarray(recs[0::7][:48]),
+    cached_bank_frames_match_render(P, padded, caps, np.ascontiguousarray(recs[0::7][:48]),
                                      np.ascontiguousarray(recs[3::40][:9]), 4)
 
 
@@ -78,34 +79,17 @@ def test_reduced_crop_split_equals_unsplit_bitwise():
     split step: the matrix's two steps at (128, 0.5, crop 128) in two contexts,
     unsplit and split, frames, records and outputs equal bit for bit."""
     P, padded, caps, recs, layout, acts = _reduced_batch((128, 0.5, 128, 128))
-    n, S, L = len(recs), P.size, lib()
-    out = []
-    for split in (0, 1):
-        dw = DevWorld(P, padded, caps)
-        check(L.cbev_set_split_step(dw.ctx, split), "split_step")
-        d_recs = torch.from_numpy(recs.copy()).cuda()
-        frames = torch.zeros((n, S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(frames), 1, None), "reset")
-        b = dict(rew=torch.zeros(n, dtype=torch.float64, device="cuda"),
-                 term=torch.zeros(n, dtype=torch.uint8, device="cuda"),
-                 trunc=torch.zeros(n, dtype=torch.uint8, device="cuda"),
-                 cause=torch.zeros(n, dtype=torch.int32, device="cuda"),
-                 info=torch.zeros((n, 16), dtype=torch.float32, device="cuda"))
-        out.append((dw, d_recs, frames, b))
-    (dA, rA, fA, bA), (dB, rB, fB, bB) = out
+    lanes = make_lanes(P, padded, caps, recs, None, 1, [dict(split=0), dict(split=1)], stats=False)
+    A, B = lanes
     torch.cuda.synchronize()
-    assert torch.equal(fA, fB), "reset frames"
+    assert torch.equal(A.ring, B.ring), "reset frames"
     for t in range(len(acts)):
-        a = torch.from_numpy(np.ascontiguousarray(acts[t])).cuda()
-        for dw, d_recs, frames, b in out:
-            check(L.cbev_step(dw.ctx, ptr(d_recs), n, ptr(a), ptr(frames), ptr(b["rew"]), ptr(b["term"]), ptr(b["trunc"]),
-                              ptr(b["cause"]), ptr(b["info"]), None), "step")
-        torch.cuda.synchronize()
-        assert torch.equal(fA, fB), (t, "frames")
-        assert torch.equal(rA, rB), (t, "records")
-        for k in bA:
-            assert torch.equal(bA[k], bB[k]), (t, k)
-    assert error_flags(dA.ctx) == 0 and error_flags(dB.ctx) == 0
+        step_all(lanes, acts[t], t)
+        assert torch.equal(A.ring, B.ring), (t, "frames")
+        assert torch.equal(A.recs, B.recs), (t, "records")
+        for k in A.out:
+            assert torch.equal(A.out[k], B.out[k]), (t, k)
+    assert error_flags(A.dw.ctx) == 0 and error_flags(B.dw.ctx) == 0
 
 
 def _create(P):

@@ -27,9 +27,9 @@ torch = pytest.importorskip("torch")
 import episode_fixture as EF
 from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import check, lib
+from episode_fixture import BOUND, Deviation, compare_reset, compare_step, compare_summary, pack_episode, world_of
+from gpu_harness import DevWorld, EpisodeStatsOn, error_flags, out_bufs, ptr
 from helpers import CAPS_FULL
-from test_episode_golden import BOUND, Deviation, compare_reset, compare_step, compare_summary, pack_episode, world_of
-from test_gpu_parity import DevWorld, EpisodeStatsOn, error_flags, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -90,11 +90,7 @@ def test_device_replays_the_reference_episodes(config, split):
     for e, ep in enumerate(eps):
         v = LY.RecordView(h[e], layout)
         compare_reset(ep, v, dev, None)
-    rew = torch.zeros(n, dtype=torch.float64, device="cuda")
-    term = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    trunc = torch.zeros_like(term)
-    cause = torch.zeros(n, dtype=torch.int32, device="cuda")
-    info = torch.zeros((n, 16), dtype=torch.float32, device="cuda")
+    rew, term, trunc, cause, info = out_bufs(n).values()
     cont = P.action_kind == 1
     compared = rows_seen = 0
     for t in range(max(ep.n_steps for ep in eps)):

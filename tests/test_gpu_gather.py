@@ -8,7 +8,6 @@ the bar is a bit-exact round trip of the step's own outputs.
 """
 from __future__ import annotations
 
-import ctypes
 import socket
 
 import numpy as np
@@ -18,22 +17,10 @@ torch = pytest.importorskip("torch")
 
 from carlabev_env_amd._lib import lib
 from carlabev_env_amd.sharding import FrameGather, pack_frames, payload_bytes, unpack_frames
+from gpu_harness import P_, DevWorld
 from helpers import bench_caps, world
 
 pytestmark = pytest.mark.gpu
-
-P_ = ctypes.c_void_p
-
-
-class Ctx:
-    def __init__(self, size):
-        cfg, P, padded, layout, builder = world(size=size, caps=bench_caps(2))
-        self.ctx = P_()
-        assert lib().cbev_create(ctypes.byref(P), ctypes.byref(bench_caps(2).c()), 0, ctypes.byref(self.ctx)) == 0
-        assert lib().cbev_set_map(self.ctx, padded.ctypes.data_as(P_), padded.nbytes) == 0
-
-    def __del__(self):
-        lib().cbev_destroy(self.ctx)
 
 
 def torch_pack(fr):
@@ -46,7 +33,8 @@ def test_pack_unpack_frames_device(S):
     """Every palette id 0..15 in both nibbles, an odd env count, on a side stream
     (the default stream argument is the current torch stream), and unpacking
     from a receive-buffer view at a nonzero rank offset."""
-    c = Ctx(S)
+    cfg, P, padded, layout, builder = world(size=S, caps=bench_caps(2))
+    c = DevWorld(P, padded, bench_caps(2))
     n = 7
     g = torch.Generator().manual_seed(S)
     fr = torch.randint(0, 16, (n, S, S), dtype=torch.uint8, generator=g)

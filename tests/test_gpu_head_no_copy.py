@@ -18,21 +18,21 @@ torch = pytest.importorskip("torch")
 import edge_cases as EC
 from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import check, lib
-from test_gpu_parity import P_, _counts, error_flags, ptr, reset_rows
-from test_gpu_reset_preview import (F, N_BANK, UNSPLIT_AND_PREVIEW, _case, _delta, _make, _prime, _pv, _set_term, _term,
-                                    _world)
-from test_gpu_thin_head import CAPS_LONG2, _assert_same, _long_records, _reset_terminated, _step
+from gpu_harness import (P_, assert_same, assert_same_outputs, error_flags, preview_counts, ptr, reset_counts,
+                         reset_rows, reset_terminated_all, set_term, step_all, term_of)
+from gpu_scenes import (CAPS_LONG2, N_BANK, UNSPLIT_AND_PREVIEW, long_records, preview_delta, prime, primed_case,
+                        split_lanes, wall_world)
 
 pytestmark = pytest.mark.gpu
 
 
-def _same(ctxs, t, want=None):
-    """_assert_same and the preview counters: the unsplit step has no head, the split
+def _same(lanes, t, want=None):
+    """assert_same and the preview counters: the unsplit step has no head, the split
     one's are `want` (when given)."""
-    _assert_same(ctxs, t)
-    assert _pv(ctxs[0]) == (0, 0), t
+    assert_same(lanes, t)
+    assert preview_counts(lanes[0]) == (0, 0), t
     if want is not None:
-        assert _pv(ctxs[1]) == want, (t, _pv(ctxs[1]), want)
+        assert preview_counts(lanes[1]) == want, (t, preview_counts(lanes[1]), want)
 
 
 def _off_road_dy(classes, x, y):
@@ -52,7 +52,7 @@ def _off_road_dy(classes, x, y):
 
 
 def _records(n, size, seed0, off_every, lengths=(65, 127, 128, 64, 33)):
-    """test_gpu_thin_head's _long_records without actors at any size: every
+    """gpu_scenes.long_records without actors at any size: every
     off_every-th record starts inside a wall and terminates in its first step."""
     _, _, classes = EC.authored_world(size)
     specs = [dataclasses.replace(EC.long_route_spec(lengths[e % len(lengths)], size, seed=seed0 + e), vehicles=[],
@@ -68,21 +68,21 @@ def _records(n, size, seed0, off_every, lengths=(65, 127, 128, 64, 33)):
     return recs, layout
 
 
-def _loop(ctxs, acts, steps):
+def _loop(lanes, acts, steps):
     """The canonical loop; returns the resets folded per step and how often an env
     terminated in the very step that took its reset."""
     n = acts.shape[1]
     was_reset = np.zeros(n, bool)
     reset_then_term, folded = 0, []
     for t in range(steps):
-        _step(ctxs, acts[t], t)
-        _same(ctxs, t)
-        tn = _term(ctxs[0])
+        step_all(lanes, acts[t], t)
+        _same(lanes, t)
+        tn = term_of(lanes[0])
         reset_then_term += int(np.sum(was_reset & tn))
         was_reset = tn
         if t < steps - 1:
             folded.append(int(tn.sum()))
-            _reset_terminated(ctxs)
+            reset_terminated_all(lanes)
     return folded, reset_then_term
 
 
@@ -114,13 +114,13 @@ def test_canonical_loop_equals_unsplit(n, head_ne, monkeypatch):
     monkeypatch.setenv("CBEV_HEAD_NE", str(head_ne))
     steps = 40
     P, padded, _ = EC.authored_world(128)
-    recs, _ = _long_records(n, CAPS_LONG2, 100, off_every=2)
-    bank, _ = _long_records(N_BANK, CAPS_LONG2, 500, off_every=3)
-    ctxs = _make(P, padded, CAPS_LONG2, recs, bank, UNSPLIT_AND_PREVIEW)
-    folded, reset_then_term = _loop(ctxs, _acts(P, steps, n, 19), steps)
+    recs, _ = long_records(n, CAPS_LONG2, 100, off_every=2)
+    bank, _ = long_records(N_BANK, CAPS_LONG2, 500, off_every=3)
+    lanes = split_lanes(P, padded, CAPS_LONG2, recs, bank, UNSPLIT_AND_PREVIEW)
+    folded, reset_then_term = _loop(lanes, _acts(P, steps, n, 19), steps)
     assert sum(folded[1:]) >= 10 and reset_then_term > 0
-    assert _pv(ctxs[1]) == (sum(folded[1:]), folded[0])
-    assert error_flags(ctxs[0][0].ctx) == 0 and error_flags(ctxs[1][0].ctx) == 0
+    assert preview_counts(lanes[1]) == (sum(folded[1:]), folded[0])
+    assert error_flags(lanes[0].dw.ctx) == 0 and error_flags(lanes[1].dw.ctx) == 0
 
 
 # ---------------------------------------------------------------------- 2. compositions of a group
@@ -134,22 +134,22 @@ def test_group_compositions(preview):
     n = 4 * h + 3
     fast = list(range(h)) + [2 * h, 2 * h + 3, 2 * h + 6, 3 * h + 5]
     slow = [2 * h + 1, 2 * h + 4, 4 * h + 1]
-    P, padded, recs, bank, layout = _world(n, fast, n_bank=71)
-    ctxs = _make(P, padded, CAPS_LONG2, recs, bank, ((0, 1), (1, preview)))
+    P, padded, recs, bank, layout = wall_world(n, fast, n_bank=71)
+    lanes = split_lanes(P, padded, CAPS_LONG2, recs, bank, ((0, 1), (1, preview)))
     acts = np.ones(n, np.int32)
-    (h0, f0), term1 = _prime(ctxs, n, fast, acts)
+    (h0, f0), term1 = prime(lanes, n, fast, acts)
     assert not term1[slow].any()
-    tc = _counts(lib(), ctxs[1][0], n)  # (before the reset is recorded: reading the counts applies a pending one)
-    _reset_terminated(ctxs)
+    tc = reset_counts(lib(), lanes[1].dw, n)  # (before the reset is recorded: reading the counts applies a pending one)
+    reset_terminated_all(lanes)
     mask = np.zeros(n, np.uint8)
     mask[fast] = 1
     mask[slow] = 1
-    _set_term(ctxs, mask)
-    _step(ctxs, acts, 2)
+    set_term(lanes, mask)
+    step_all(lanes, acts, 2)
     want = (h0 + len(fast), f0 + len(slow)) if preview else (0, f0 + len(fast) + len(slow))
-    _same(ctxs, 2, want)
+    _same(lanes, 2, want)
     assert mask[:h].all() and not mask[h:2 * h].any() and mask[2 * h:3 * h].sum() == 5 and mask[3 * h:4 * h].sum() == 1
-    hr = ctxs[1][3].cpu().numpy()
+    hr = lanes[1].recs.cpu().numpy()
     ids, rows = reset_rows(mask, tc, 71)
     assert len(ids) == int(mask.sum())
     for e, row in zip(ids, rows):
@@ -157,9 +157,9 @@ def test_group_compositions(preview):
     for e in np.flatnonzero(mask == 0):
         assert LY.RecordView(hr[e], layout).i("SCENE_ID") == e
     # and the step after it, whose tail and raster read the records this one's tail completed
-    _reset_terminated(ctxs)
-    _step(ctxs, acts, 3)
-    _same(ctxs, 3)
+    reset_terminated_all(lanes)
+    step_all(lanes, acts, 3)
+    _same(lanes, 3)
 
 
 # ---------------------------------------------------------------------- 3. a stale record
@@ -202,18 +202,18 @@ def test_stale_record_is_read_by_neither_role(geo):
     world = EC.authored_world(128) if geo is None else EC.reduced_world(*geo)
     P, padded = world[0], world[1]
     recs, bank, layout = _stale_world(world, n)
-    ctxs = _make(P, padded, CAPS_LONG2, recs, bank[:n], UNSPLIT_AND_PREVIEW)
+    lanes = split_lanes(P, padded, CAPS_LONG2, recs, bank[:n], UNSPLIT_AND_PREVIEW)
     acts = np.ones(n, np.int32)
-    _step(ctxs, acts, 0)
-    _same(ctxs, 0)
+    step_all(lanes, acts, 0)
+    _same(lanes, 0)
     mask = np.ones(n, np.uint8)
     mask[[3, 8]] = 0
-    _set_term(ctxs, mask)
-    tc = _counts(lib(), ctxs[1][0], n)
-    _reset_terminated(ctxs)
-    _step(ctxs, acts, 1)
-    _same(ctxs, 1)
-    hr = ctxs[1][3].cpu().numpy()
+    set_term(lanes, mask)
+    tc = reset_counts(lib(), lanes[1].dw, n)
+    reset_terminated_all(lanes)
+    step_all(lanes, acts, 1)
+    _same(lanes, 1)
+    hr = lanes[1].recs.cpu().numpy()
     ids, rows = reset_rows(mask, tc, n)
     for e, row in zip(ids, rows):
         _rest_equals_row(hr[e], bank[row], layout)
@@ -222,9 +222,9 @@ def test_stale_record_is_read_by_neither_role(geo):
     if geo is not None:  # the reset envs' items took the checked path
         assert not any(LY.RecordView(hr[e], layout).i("RS_FAST") & 1 for e in ids)
     # the preview path too: every env again, from the previews of the envs that terminated
-    _reset_terminated(ctxs)
-    _step(ctxs, acts, 2)
-    _same(ctxs, 2)
+    reset_terminated_all(lanes)
+    step_all(lanes, acts, 2)
+    _same(lanes, 2)
 
 
 # ---------------------------------------------------------------------- 4. an edited mask
@@ -233,19 +233,19 @@ def test_mask_byte_cleared_after_reset_terminated_keeps_the_old_episode_whole():
     it stands at the launch, and the tail and the raster follow the head's word,
     not the byte: the record stays the old episode's in every byte the step does
     not compute. A byte set for an env that never terminated is a reset."""
-    P, bank, layout, ctxs, acts, base, term1 = _case()
-    before = ctxs[1][3].cpu().numpy().copy()
-    tc = _counts(lib(), ctxs[1][0], len(acts))  # (before the reset is recorded: reading the counts applies a pending one)
-    _reset_terminated(ctxs)
-    mask = _term(ctxs[1]).astype(np.uint8)
+    P, bank, layout, lanes, acts, base, term1 = primed_case()
+    before = lanes[1].recs.cpu().numpy().copy()
+    tc = reset_counts(lib(), lanes[1].dw, len(acts))  # (before the reset is recorded: reading the counts applies a pending one)
+    reset_terminated_all(lanes)
+    mask = term_of(lanes[1]).astype(np.uint8)
     assert mask[4] and not mask[[0, 9]].any()
     mask[4] = 0
     mask[[0, 9]] = 1
-    _set_term(ctxs, mask)
-    _step(ctxs, acts, 2)
-    _same(ctxs, 2)
-    assert _delta(ctxs, base) == (int(term1.sum()) - 1, 2)
-    hr = ctxs[1][3].cpu().numpy()
+    set_term(lanes, mask)
+    step_all(lanes, acts, 2)
+    _same(lanes, 2)
+    assert preview_delta(lanes, base) == (int(term1.sum()) - 1, 2)
+    hr = lanes[1].recs.cpu().numpy()
     _rest_equals_row(hr[4], before[4], layout)
     ids, rows = reset_rows(mask, tc, N_BANK)
     assert {0, 9} <= set(ids.tolist()) and 4 not in ids
@@ -259,10 +259,10 @@ def test_size_256_four_tiles_read_the_row():
     P, padded, _ = EC.authored_world(256)
     recs, _ = _records(n, 256, 100, off_every=2)
     bank, _ = _records(N_BANK, 256, 500, off_every=3)
-    ctxs = _make(P, padded, CAPS_LONG2, recs, bank, UNSPLIT_AND_PREVIEW)
-    folded, reset_then_term = _loop(ctxs, _acts(P, steps, n, 5), steps)
+    lanes = split_lanes(P, padded, CAPS_LONG2, recs, bank, UNSPLIT_AND_PREVIEW)
+    folded, reset_then_term = _loop(lanes, _acts(P, steps, n, 5), steps)
     assert sum(folded[1:]) >= 5 and reset_then_term > 0
-    assert _pv(ctxs[1]) == (sum(folded[1:]), folded[0])
+    assert preview_counts(lanes[1]) == (sum(folded[1:]), folded[0])
 
 
 # ---------------------------------------------------------------------- 6. graph capture
@@ -270,9 +270,9 @@ def test_captured_step_replayed_twice():
     """A step captured while a reset is pending, replayed twice against the eager
     unsplit run: the tail and the raster of each replay take the rows the head of
     that replay chose."""
-    P, bank, layout, ctxs, acts, base, term1 = _case(extra_off=[(e + lib().cbev_bank_stride(N_BANK)) % N_BANK for e in (1, 4, 17)])
+    P, bank, layout, lanes, acts, base, term1 = primed_case(extra_off=[(e + lib().cbev_bank_stride(N_BANK)) % N_BANK for e in (1, 4, 17)])
     L = lib()
-    A, B = ctxs
+    A, B = lanes
     n = len(acts)
     a = torch.from_numpy(acts).cuda()
 
@@ -281,7 +281,7 @@ def test_captured_step_replayed_twice():
         check(L.cbev_step(dw.ctx, ptr(d_recs), n, ptr(a), ptr(ring[2]), ptr(b["rew"]), ptr(b["term"]),
                           ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), stream), "step")
 
-    _reset_terminated([B])
+    reset_terminated_all([B])
     side = torch.cuda.Stream()
     g = torch.cuda.CUDAGraph()
     side.wait_stream(torch.cuda.current_stream())
@@ -291,14 +291,12 @@ def test_captured_step_replayed_twice():
     torch.cuda.synchronize()
     resets = []
     for rep in range(2):
-        resets.append(int(_term(A).sum()))
-        _reset_terminated([A])
+        resets.append(int(term_of(A).sum()))
+        reset_terminated_all([A])
         step(A, None)
         g.replay()
         torch.cuda.synchronize()
-        for k in ("rew", "term", "trunc", "cause", "info"):
-            assert torch.equal(A[5][k], B[5][k]), (rep, k)
-        assert torch.equal(A[3], B[3]) and torch.equal(A[4], B[4]), (rep, "records / ring")
-        assert np.array_equal(_counts(L, A[0], n), _counts(L, B[0], n)), (rep, "reset counts")
+        assert_same_outputs(A, B, rep)
+        assert np.array_equal(reset_counts(L, A.dw, n), reset_counts(L, B.dw, n)), (rep, "reset counts")
     assert resets[1] >= 3
-    assert _delta(ctxs, base) == (resets[0], resets[1]) and _pv(A) == (0, 0)
+    assert preview_delta(lanes, base) == (resets[0], resets[1]) and preview_counts(A) == (0, 0)

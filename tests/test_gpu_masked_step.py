@@ -11,8 +11,6 @@ its frame and its last term / trunc / cause / info stay, and its reward is 0.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -21,69 +19,15 @@ torch = pytest.importorskip("torch")
 import oracle as O
 from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import ERR_ACTION_INDEX, check, lib
+from gpu_harness import (KEYS, P_, DevWorld, EpisodeStatsOn, assert_same, assert_same_outputs, error_flags, flush_all,
+                         out_bufs, ptr, reset_counts, reset_terminated_all, step_masked, step_repeat, termination_count)
+from gpu_scenes import (EGO_ONLY, compare_records, deferred_pair, ego_only_64, eval_actions, eval_cfg, eval_pair,
+                        info_of, mask_stream, twins)
 from helpers import action_stream, bench_caps, build_records, world
-from test_gpu_action_repeat import step_repeat
-from test_gpu_parity import (DevWorld, EpisodeStatsOn, P_, _counts, _deferred_pair, _same_stats, compare_records,
-                             error_flags, info_of, ptr)
-from test_gpu_split_step import _bufs, _split_pair
 
 pytestmark = pytest.mark.gpu
 
 CBEV_EINVAL = -1
-KEYS = ("rew", "term", "trunc", "cause", "info")
-
-
-def step_masked(L, dw, d_recs, n, a, act, k, prev, frames, b, stream=None):
-    return L.cbev_step_masked(dw.ctx, ptr(d_recs), n, ptr(a), ptr(act), k, ptr(prev), ptr(frames), ptr(b["rew"]),
-                              ptr(b["term"]), ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), stream)
-
-
-def _nterm(L, dw):
-    c = ctypes.c_int64()
-    check(L.cbev_termination_count(dw.ctx, ctypes.byref(c)), "termination_count")
-    return c.value
-
-
-def mask_stream(n, steps, seed):
-    """The active masks of a run, bool[steps][n]. Envs are active with
-    probability 0.65; with more than 32 envs, envs 0-15 (a whole ego workgroup
-    at 16 envs per workgroup) are all inactive on every fourth step, 16-31 stay
-    mixed and the rest is the ragged tail; every third env is inactive on the
-    first step after the reset."""
-    rng = np.random.default_rng(seed)
-    m = rng.random((steps, n)) < 0.65
-    if n > 32:
-        m[1::4, :16] = False
-    m[0, ::3] = False
-    m[0, 1] = True
-    return m
-
-
-def ego_only_64(n):
-    """n ego-only scenes at size 64 (the scene generator builds none at this
-    size): routes of 24 to 64 points along the map's longest straight road at
-    bench config 2's capacities; every third env starts beside the road, every
-    fourth at a heading across it."""
-    import edge_cases as EC
-    from carlabev_env_amd.scene_pack import SceneSpec
-    caps = bench_caps(2)
-    P, padded, _ = EC.authored_world(64)
-    y, x0, x1 = EC._road_run(64)
-    specs = []
-    for e in range(n):
-        m = 24 + 5 * e
-        sp = max(1, min(3, (x1 - x0 - 8) // (m - 1)))
-        rx = [x0 + 4 + sp * i for i in range(m)]
-        ry = [y + ((i // 8) % 2) for i in range(m)]
-        specs.append(SceneSpec(agent_rx=rx, agent_ry=ry, initial_speed_mps=0.0, hero_jitter_seed=e,
-                               actor_jitter_seed=e, vehicles=[], pedestrians=[]))
-    recs, layout, views = EC.pack_records(specs, 64, caps)
-    for e, v in enumerate(views):
-        i = (3 * e) % (v.i("NROUTE") - 1)
-        EC.set_pose(v, v.cx[i] + (9.0 if e % 3 == 2 else 0.0), v.cy[i], v.cyaw[i] + (1.3 if e % 4 == 3 else 0.0),
-                    4.0 * (e % 3))
-        v.hi[LY.HI["TIDX"]] = i
-    return P, padded, caps, recs, layout
 
 
 def run_masked_parity(kinds, n, steps, k, size=128, seed0=0, act_seed=1234, caps=None, mask_seed=0, F=2, recs=None,
@@ -133,7 +77,7 @@ def run_masked_parity(kinds, n, steps, k, size=128, seed0=0, act_seed=1234, caps
         ring = torch.zeros((F, n, S, S), dtype=torch.uint8, device="cuda")
         check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), F, None), "reset")
         st = EpisodeStatsOn(dw.ctx, n)
-        b = _bufs(n)
+        b = out_bufs(n)
     hist = np.zeros(k + 1, np.int64)
     seen_active, seen_inactive, ended = np.zeros(n, bool), np.zeros(n, bool), np.zeros(n, bool)
     cov = dict(term_then_inactive=0, inactive_live=0, inactive_first=0)
@@ -194,8 +138,8 @@ def run_masked_parity(kinds, n, steps, k, size=128, seed0=0, act_seed=1234, caps
         assert np.allclose(got, h_info, rtol=1e-6, atol=1e-6), (t, "info")
         on = np.flatnonzero(act)
         st.check(t, wrote, on, [views[e] for e in on], h_cause[on])
-        assert np.array_equal(_counts(L, dw, n).astype(np.int64), tcount), (t, "reset counts")
-        assert _nterm(L, dw) == int(tcount.sum()), (t, "termination count")
+        assert np.array_equal(reset_counts(L, dw, n).astype(np.int64), tcount), (t, "reset counts")
+        assert termination_count(L, dw) == int(tcount.sum()), (t, "termination count")
     if device:
         assert error_flags(dw.ctx) == 0
     cov.update(hist=hist.tolist(), both=bool(np.all(seen_active & seen_inactive)))
@@ -240,28 +184,6 @@ def test_masked_step_at_size_64_ego_only():
     _covers_every_case(cov, every_substep=False)
 
 
-def _twins(n, caps, size, kinds, seed0, bank_seed0, n_bank=53, F=3):
-    """_split_pair's two contexts with the split step and the deferred reset off
-    in both: cbev_step_repeat then runs the kernels the masked step gates."""
-    P, ctxs = _split_pair(n, caps, size, kinds, seed0, bank_seed0, n_bank=n_bank, F=F)
-    L = lib()
-    for dw, *_ in ctxs:
-        check(L.cbev_set_split_step(dw.ctx, 0), "split off")
-        check(L.cbev_set_deferred_reset(dw.ctx, 0), "deferred off")
-    return P, ctxs
-
-
-def _same_everything(L, A, B, t, n):
-    (dA, _, _, rA, gA, bA), (dB, _, _, rB, gB, bB) = A, B
-    for key in KEYS:
-        assert torch.equal(bA[key], bB[key]), (t, key)
-    assert torch.equal(rA, rB), (t, "records")
-    assert torch.equal(gA, gB), (t, "ring")
-    assert _same_stats(bA["stats"], bB["stats"], t, n), (t, "episode stats")
-    assert np.array_equal(bA["stats"].counts.cpu().numpy(), bB["stats"].counts.cpu().numpy()), (t, "counts")
-    assert np.array_equal(_counts(L, dA, n), _counts(L, dB, n)), (t, "reset counts")
-
-
 @pytest.mark.parametrize("config,kinds,k", [(2, ("rt_no_traffic_v1",), 1), (2, ("rt_no_traffic_v1",), 4),
                                             (3, ("rt_hard_v1", "rt_medium_v1"), 4)])
 def test_all_active_equals_step_repeat_bitwise(config, kinds, k):
@@ -269,11 +191,11 @@ def test_all_active_equals_step_repeat_bitwise(config, kinds, k):
     bytes everywhere, through cbev_reset_terminated after each step (which reads
     the context's last term buffer and env count, set by either call)."""
     n, n_bank, F, steps = 19, 53, 3, 20
-    P, ctxs = _twins(n, bench_caps(config), 128, kinds, 10_419, 14_419, n_bank=n_bank, F=F)
+    P, lanes = twins(n, bench_caps(config), 128, kinds, 10_419, 14_419, n_bank=n_bank, F=F)
     L = lib()
     acts = action_stream(P, n, steps, seed=5)
     ones = torch.ones(n, dtype=torch.uint8, device="cuda")
-    A, B = ctxs
+    A, B = lanes
     for t in range(steps):
         a = torch.from_numpy(np.ascontiguousarray(acts[t])).cuda()
         dw, _, _, d_recs, ring, b = A
@@ -281,23 +203,21 @@ def test_all_active_equals_step_repeat_bitwise(config, kinds, k):
         dw, _, _, d_recs, ring, b = B
         check(step_masked(L, dw, d_recs, n, a, ones, k, ring[t % F], ring[(t + 1) % F], b), "step_masked")
         torch.cuda.synchronize()
-        _same_everything(L, A, B, t, n)
-        for dw, d_bank, bf, d_recs, ring, b in ctxs:
-            check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n, ptr(d_bank), n_bank, ptr(bf), ptr(ring), F, None),
-                  "reset_terminated")
+        assert_same(lanes, t)
+        reset_terminated_all(lanes)
     torch.cuda.synchronize()
-    assert torch.equal(A[3], B[3]) and torch.equal(A[4], B[4])
-    assert int(_counts(L, A[0], n).sum()) > 0
-    for dw, *_ in ctxs:
+    assert torch.equal(A.recs, B.recs) and torch.equal(A.ring, B.ring)
+    assert int(reset_counts(L, A.dw, n).sum()) > 0
+    for dw, *_ in lanes:
         assert error_flags(dw.ctx) == 0
 
 
 @pytest.mark.parametrize("same_slot", [False, True])
 def test_all_inactive_touches_nothing_but_reward_and_frames(same_slot):
     n, F, k = 21, 2, 2
-    P, ctxs = _twins(n, bench_caps(3), 128, ("rt_hard_v1",), 10_519, 14_519, F=F)
+    P, lanes = twins(n, bench_caps(3), 128, ("rt_hard_v1",), 10_519, 14_519, F=F)
     L = lib()
-    dw, d_bank, bf, d_recs, ring, b = ctxs[0]
+    dw, d_bank, bf, d_recs, ring, b = lanes[0]
     a = torch.ones(n, dtype=torch.int32, device="cuda")
     ones, zeros = torch.ones(n, dtype=torch.uint8, device="cuda"), torch.zeros(n, dtype=torch.uint8, device="cuda")
     check(step_masked(L, dw, d_recs, n, a, ones, k, ring[1], ring[0], b), "step_masked")  # step 0: some terminate
@@ -305,7 +225,7 @@ def test_all_inactive_touches_nothing_but_reward_and_frames(same_slot):
     assert int(b["term"].sum()) > 0 and int((b["term"] == 0).sum()) > 0
     st = b["stats"]
     before = [d_recs.clone(), st.stats.clone(), st.rows.clone()] + [b[key].clone() for key in KEYS[1:]]
-    ring0, counts0, nterm0 = ring.clone(), _counts(L, dw, n), _nterm(L, dw)
+    ring0, counts0, nterm0 = ring.clone(), reset_counts(L, dw, n), termination_count(L, dw)
     b["rew"].fill_(3.5)
     dst = ring[0] if same_slot else ring[1]
     assert not torch.equal(ring[0], ring[1])
@@ -317,15 +237,15 @@ def test_all_inactive_touches_nothing_but_reward_and_frames(same_slot):
     assert torch.equal(ring[0], ring0[0])
     assert torch.equal(ring[1], ring0[1] if same_slot else ring0[0])
     assert int(st.counts[1 % st.RING].item()) == 0  # step 1 wrote no episode row
-    assert np.array_equal(_counts(L, dw, n), counts0) and _nterm(L, dw) == nterm0
+    assert np.array_equal(reset_counts(L, dw, n), counts0) and termination_count(L, dw) == nterm0
     assert error_flags(dw.ctx) == 0
 
 
 def test_an_inactive_env_raises_no_action_error():
     n = 21
-    P, ctxs = _twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_619, 14_619, F=2)
+    P, lanes = twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_619, 14_619, F=2)
     L = lib()
-    dw, d_bank, bf, d_recs, ring, b = ctxs[0]
+    dw, d_bank, bf, d_recs, ring, b = lanes[0]
     a = torch.ones(n, dtype=torch.int32, device="cuda")
     a[5], a[18] = 100, -100  # out of range for discrete9_v1
     act = torch.ones(n, dtype=torch.uint8, device="cuda")
@@ -364,7 +284,7 @@ def test_masked_step_under_graph_capture():
     mask tensor edited between the replays equals two eager calls with those
     masks from the same start: the mask is read when the launches run."""
     n, F, k = 19, 2, 2
-    P, ctxs = _twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_719, 14_719, F=F)
+    P, lanes = twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_719, 14_719, F=F)
     L = lib()
     acts = torch.ones(n, dtype=torch.int32, device="cuda")
     rng = np.random.default_rng(3)
@@ -377,7 +297,7 @@ def test_masked_step_under_graph_capture():
         check(step_masked(L, dw, d_recs, n, acts, m, k, ring[0], ring[1], b,
                           P_(torch.cuda.current_stream().cuda_stream)), "step_masked")
 
-    A, B = ctxs
+    A, B = lanes
     step(A, masks[0])  # one eager call each: the kernels are loaded before the capture
     step(B, m_graph)
     torch.cuda.synchronize()
@@ -388,18 +308,15 @@ def test_masked_step_under_graph_capture():
         with torch.cuda.graph(g, stream=side):
             step(B, m_graph)
     torch.cuda.synchronize()
-    assert torch.equal(A[3], B[3])  # the capture ran nothing
+    assert torch.equal(A.recs, B.recs)  # the capture ran nothing
     for rep in (1, 2):
         step(A, masks[rep])
         m_graph.copy_(masks[rep])
         g.replay()
         torch.cuda.synchronize()
-        for key in KEYS:
-            assert torch.equal(A[5][key], B[5][key]), (rep, key)
-        assert torch.equal(A[3], B[3]), (rep, "records")
-        assert torch.equal(A[4], B[4]), (rep, "ring")
-        assert torch.equal(B[5]["rew"][m_graph == 0], torch.zeros_like(B[5]["rew"])[m_graph == 0]), rep
-    assert int(A[5]["term"].sum()) > 0
+        assert_same_outputs(A, B, rep)
+        assert torch.equal(B.out["rew"][m_graph == 0], torch.zeros_like(B.out["rew"])[m_graph == 0]), rep
+    assert int(A.out["term"].sum()) > 0
 
 
 def test_pending_deferred_reset_is_applied_before_the_masked_step():
@@ -407,9 +324,9 @@ def test_pending_deferred_reset_is_applied_before_the_masked_step():
     masked step launches the recorded reset before substep 1) against the same
     with it off: everything equal after every step."""
     n, B, F, k, steps = 45, 13, 3, 2, 20
-    P, layout, ctxs = _deferred_pair(n, B, F, bench_caps(2), 7100, 17100)
+    P, layout, lanes = deferred_pair(n, B, F, bench_caps(2), 7100, 17100)
     L = lib()
-    for dw, d_bank, bf, d_recs, ring, b in ctxs:  # every second env starts off the road
+    for dw, d_bank, bf, d_recs, ring, b in lanes:  # every second env starts off the road
         check(L.cbev_flush(dw.ctx), "flush")
         h = d_recs.cpu().numpy()
         for e in range(0, n, 2):
@@ -417,38 +334,28 @@ def test_pending_deferred_reset_is_applied_before_the_masked_step():
         d_recs.copy_(torch.from_numpy(h))
     acts = action_stream(P, n, steps, seed=21)
     masks = mask_stream(n, steps, 145)
-    A, Bc = ctxs
+    A, Bc = lanes
     pending = 0
     for t in range(steps):
         a = torch.from_numpy(np.ascontiguousarray(acts[t])).cuda()
         m = torch.from_numpy(masks[t].astype(np.uint8)).cuda()
-        pending += L.cbev_reset_pending(Bc[0].ctx)
-        for dw, d_bank, bf, d_recs, ring, b in ctxs:
+        pending += L.cbev_reset_pending(Bc.dw.ctx)
+        for dw, d_bank, bf, d_recs, ring, b in lanes:
             check(step_masked(L, dw, d_recs, n, a, m, k, ring[t % F], ring[(t + 1) % F], b), "step_masked")
             assert L.cbev_reset_pending(dw.ctx) == 0
         torch.cuda.synchronize()
-        (dA, _, _, rA, gA, bA), (dB, _, _, rB, gB, bB) = A, Bc
-        for key in KEYS:
-            assert torch.equal(bA[key], bB[key]), (t, key)
-        assert torch.equal(rA, rB), (t, "records")
-        assert torch.equal(gA, gB), (t, "ring")
-        assert _same_stats(bA["stats"], bB["stats"], t, n), (t, "episode stats")
-        assert np.array_equal(_counts(L, dA, n), _counts(L, dB, n)), (t, "reset counts")
-        for dw, d_bank, bf, d_recs, ring, b in ctxs:
-            check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n, ptr(d_bank), B, ptr(bf), ptr(ring), F, None),
-                  "reset_terminated")
-    for dw, *_ in ctxs:
-        check(L.cbev_flush(dw.ctx), "flush")
-    torch.cuda.synchronize()
-    assert torch.equal(A[3], Bc[3]) and torch.equal(A[4], Bc[4])
-    assert pending >= steps - 1 and int(_counts(L, A[0], n).sum()) > 0
+        assert_same(lanes, t)
+        reset_terminated_all(lanes)
+    flush_all(lanes)
+    assert torch.equal(A.recs, Bc.recs) and torch.equal(A.ring, Bc.ring)
+    assert pending >= steps - 1 and int(reset_counts(L, A.dw, n).sum()) > 0
 
 
 def test_refusals_leave_a_live_context_untouched():
     n, F = 19, 2
-    P, ctxs = _twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_819, 14_819, F=F)
+    P, lanes = twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_819, 14_819, F=F)
     L = lib()
-    dw, d_bank, bf, d_recs, ring, b = ctxs[0]
+    dw, d_bank, bf, d_recs, ring, b = lanes[0]
     acts = torch.full((n,), 100, dtype=torch.int32, device="cuda")  # would raise the action flag if anything ran
     ones = torch.ones(n, dtype=torch.uint8, device="cuda")
     good = torch.ones(n, dtype=torch.int32, device="cuda")
@@ -457,7 +364,7 @@ def test_refusals_leave_a_live_context_untouched():
     st = b["stats"]
     before = [d_recs.clone(), ring.clone(), st.stats.clone(), st.rows.clone(), st.counts.clone()] + [
         b[key].clone() for key in KEYS]
-    counts0, nterm0 = _counts(L, dw, n), _nterm(L, dw)
+    counts0, nterm0 = reset_counts(L, dw, n), termination_count(L, dw)
 
     def call(act=ones, prev=ring[1], k=2, n_=n):
         return L.cbev_step_masked(dw.ctx, ptr(d_recs), n_, ptr(acts), ptr(act), k, ptr(prev), ptr(ring[0]),
@@ -471,7 +378,7 @@ def test_refusals_leave_a_live_context_untouched():
     torch.cuda.synchronize()
     after = [d_recs, ring, st.stats, st.rows, st.counts] + [b[key] for key in KEYS]
     assert all(torch.equal(x, y) for x, y in zip(before, after))
-    assert np.array_equal(_counts(L, dw, n), counts0) and _nterm(L, dw) == nterm0
+    assert np.array_equal(reset_counts(L, dw, n), counts0) and termination_count(L, dw) == nterm0
     assert error_flags(dw.ctx) == 0
     check(step_masked(L, dw, d_recs, n, good, ones, 64, ring[1], ring[0], b), "step_masked")  # the largest repeat runs
     torch.cuda.synchronize()
@@ -479,44 +386,6 @@ def test_refusals_leave_a_live_context_untouched():
 
 
 # ---------------------------------------------------------------------- the vector env
-def _eval_cfg(monkeypatch, max_actions, obs=128):
-    """The episode limit is the reward profile's (params.build_params), so a
-    small one comes from a shaping profile registered for the test."""
-    from carlabev_env_amd import EnvConfig
-    from carlabev_env_amd import config as CF
-    monkeypatch.setitem(CF.REWARD_PROFILES, "shaping_short_eval", {"family": "shaping",
-                                                                   "parameters": {"max_actions": max_actions}})
-    return EnvConfig(size=128, obs_size=(obs, obs), render_mode="rgb_array", obs_mode="bev_semantic", frame_stack=4,
-                     reward_mode="shaping", reward_profile_id="shaping_short_eval")
-
-
-EGO_ONLY = dict(route_cap=64, actor_cap=0, actor_route_cap=2, tl_cap=0)
-
-
-def _eval_pair(monkeypatch, N, max_actions, **kw):
-    from carlabev_env_amd import RandomNavigationReset, build_random_navigation_options, make_env
-    cfg = _eval_cfg(monkeypatch, max_actions)
-    envs = [make_env({"env": cfg, "num_envs": N}, num_envs=N, caps=EGO_ONLY, freeze_done=fd, **kw)
-            for fd in (True, False)]
-    opts = build_random_navigation_options(RandomNavigationReset(difficulty_id="rt_no_traffic_v1"))
-    o0, _ = envs[0].reset(seed=11, options=opts)
-    o1, _ = envs[1].reset(seed=11, options=opts)
-    assert torch.equal(o0, o1)
-    # env e is truncated after 2 + 5 e % 37 substeps (KSTEPS counts towards max_actions;
-    # the episode length counts from 0), so the envs end on different steps
-    ends = 2 + (5 * np.arange(N)) % 37
-    assert ends.max() < max_actions and len(set(ends.tolist())) > N // 2
-    o = envs[0].layout.off["hi"] + 4 * LY.HI["KSTEPS"]
-    k = torch.from_numpy((max_actions - ends).astype(np.int32)).cuda().view(torch.uint8).reshape(N, 4)
-    for env in envs:
-        env.records[:, o:o + 4] = k
-    return envs, opts
-
-
-def _eval_actions(N, t):
-    return np.random.default_rng(500 + t).choice(9, size=N, p=np.array([1, 8, 1, 1, 1, 1, 1, 1, 1]) / 16.0)
-
-
 def _run_eval(envs, N, limit):
     """Step the freeze_done env and its plain twin with the same actions until
     all_done(). Returns {env: (r, l)} of the frozen env's infos (asserting one
@@ -527,7 +396,7 @@ def _run_eval(envs, N, limit):
     steps = 0
     while not frozen.all_done():
         assert steps < limit, "the evaluation did not end"
-        a = _eval_actions(N, steps)
+        a = eval_actions(N, steps)
         rec0 = frozen.records.clone()
         _, r, term, _, infos = frozen.step(a)
         _, _, term1, _, infos1 = plain.step(a)
@@ -550,7 +419,7 @@ def _run_eval(envs, N, limit):
 
 def test_freeze_done_runs_one_episode_per_env(monkeypatch):
     N, max_actions = 24, 40
-    envs, opts = _eval_pair(monkeypatch, N, max_actions)
+    envs, opts = eval_pair(monkeypatch, N, max_actions)
     frozen, plain = envs
     assert frozen.params.max_actions == max_actions
     assert frozen.freeze_done and not plain.freeze_done
@@ -559,7 +428,7 @@ def test_freeze_done_runs_one_episode_per_env(monkeypatch):
     assert sorted(got) == list(range(N))  # every env exactly once
     for e in range(N):
         assert got[e][1] == first[e][1] and got[e][0] == first[e][0], (e, got[e], first[e])
-    assert [got[e][1] for e in range(N)] == (2 + (5 * np.arange(N)) % 37).tolist()  # ended where _eval_pair set it
+    assert [got[e][1] for e in range(N)] == (2 + (5 * np.arange(N)) % 37).tolist()  # ended where eval_pair set it
     assert steps == max(got[e][1] for e in range(N))  # the others stood still until the slowest was done
     assert frozen.termination_count() == N
     assert plain.termination_count() > N  # the plain env went on terminating
@@ -570,18 +439,18 @@ def test_freeze_done_runs_one_episode_per_env(monkeypatch):
     frozen.reset(seed=11, options=dict(opts, reset_mask=m))
     assert np.array_equal(frozen.done_mask().cpu().numpy(), ~m)
     rec0 = frozen.records.clone()
-    frozen.step(_eval_actions(N, 0))
+    frozen.step(eval_actions(N, 0))
     moved = (frozen.records != rec0).any(dim=1).cpu().numpy()
     assert np.array_equal(moved, m)
     # reset_terminated() clears the latch and the envs run again
     bank = frozen.build_bank(list(range(900, 916)), opts)
     frozen.attach_bank(bank)
     while not frozen.all_done():
-        frozen.step(_eval_actions(N, 1))
+        frozen.step(eval_actions(N, 1))
     frozen.reset_terminated()
     assert not frozen.done_mask().any()
     rec0 = frozen.records.clone()
-    _, r, term, _, _ = frozen.step(_eval_actions(N, 2))
+    _, r, term, _, _ = frozen.step(eval_actions(N, 2))
     assert (frozen.records != rec0).any(dim=1).all()
     for env in envs:
         env.close()
@@ -589,7 +458,7 @@ def test_freeze_done_runs_one_episode_per_env(monkeypatch):
 
 def test_freeze_done_with_bits_and_action_repeat(monkeypatch):
     N, max_actions = 24, 40
-    envs, _ = _eval_pair(monkeypatch, N, max_actions, obs_dtype="bits", action_repeat=2)
+    envs, _ = eval_pair(monkeypatch, N, max_actions, obs_dtype="bits", action_repeat=2)
     got, first, steps = _run_eval(envs, N, max_actions // 2 + 2)
     assert sorted(got) == list(range(N))
     for e in range(N):
@@ -605,17 +474,17 @@ def test_step_with_an_active_mask_on_a_resize_config(monkeypatch):
     inactive env's frame stays and is resized again)."""
     from carlabev_env_amd import RandomNavigationReset, build_random_navigation_options, make_env
     N = 10
-    env = make_env({"env": _eval_cfg(monkeypatch, 200, obs=96), "num_envs": N}, num_envs=N, caps=EGO_ONLY,
+    env = make_env({"env": eval_cfg(monkeypatch, 200, obs=96), "num_envs": N}, num_envs=N, caps=EGO_ONLY,
                    info_mode="none")
     opts = build_random_navigation_options(RandomNavigationReset(difficulty_id="rt_no_traffic_v1"))
     env.reset(seed=5, options=opts)
     assert env.resize and env.full is not None
     L = lib()
     dw = DevWorld(env.params, env.map_host, env.caps)
-    b = _bufs(N)
+    b = out_bufs(N)
     rng = np.random.default_rng(9)
     for t in range(6):
-        a = _eval_actions(N, t).astype(np.int32)
+        a = eval_actions(N, t).astype(np.int32)
         m = rng.random(N) < 0.5
         d_recs, fr = env.records.clone(), env.full.clone()
         ring0, head0 = env.ring.clone(), env.head

@@ -9,7 +9,6 @@ the 0 / 1 kinds, in uint8 and in one bit; there is no tolerance to choose.
 """
 from __future__ import annotations
 
-import ctypes
 import functools
 
 import numpy as np
@@ -21,49 +20,22 @@ import wrappers as W
 from carlabev_env_amd import obs_pipeline as OP
 from carlabev_env_amd._lib import OBS_BITS, OBS_F16, OBS_F32, OBS_U8, check, lib
 from carlabev_env_amd.semantics import gray_lut, rgb_lut, semantic_lut, semantic_mask_channels
-from helpers import CAPS_FULL, world
+from gpu_harness import P_, ptr
+from gpu_scenes import CODES, GUARD, cout, dtypes_of, obs_world, out_bytes
 
 pytestmark = pytest.mark.gpu
 
-P_ = ctypes.c_void_p
 MODES = ("binary", "2-class", "4-class", "5-class", "6-class", "7-class")
 VMODES = ("4-class", "5-class", "6-class", "7-class")
 FUSION = {0: "stack", 3: "vehicle_temporal", 4: "vehicle_weighted"}
-CODES = {"float32": OBS_F32, "float16": OBS_F16, "uint8": OBS_U8, "bits": OBS_BITS}
 # 35, 36, 72, 96, 7056, 16384 pixels: no multiple of 4; of 4, not 8 (float32 wide, float16 narrow); of 8, not 16;
 # of 32; of 16, not 32; the benchmark's
 SIZES = [(5, 7), (6, 6), (9, 8), (8, 12), (84, 84), (128, 128)]
-GUARD = 64
 N_MAX = 9
-
-
-def ptr(t):
-    return P_(t.data_ptr()) if t is not None else None
-
-
-class Ctx:
-    def __init__(self, hw=(128, 128)):
-        cfg, P, padded, layout, builder = world(size=128)
-        self.ctx = P_()
-        check(lib().cbev_create(ctypes.byref(P), ctypes.byref(CAPS_FULL.c()), 0, ctypes.byref(self.ctx)), "create")
-        check(lib().cbev_set_map(self.ctx, padded.ctypes.data_as(P_), padded.nbytes), "set_map")
-        if hw != (128, 128):
-            check(lib().cbev_set_obs_size(self.ctx, hw[0], hw[1]), "set_obs_size")
-
-    def __del__(self):
-        lib().cbev_destroy(self.ctx)
 
 
 def kinds_of(mode):
     return (0, 3, 4) if mode in VMODES else (0,)
-
-
-def dtypes_of(kind):
-    return ("float32", "float16") if kind == 4 else ("float32", "float16", "uint8", "bits")
-
-
-def cout(kind, F, C):
-    return {0: F * C, 3: C + 2, 4: C}[kind]
 
 
 def convert(ref: np.ndarray, dt: str) -> np.ndarray:
@@ -76,10 +48,6 @@ def convert(ref: np.ndarray, dt: str) -> np.ndarray:
         return ref.astype(np.uint8)
     planes = ref.reshape(*ref.shape[:-2], -1) if ref.ndim >= 3 else ref
     return np.packbits(planes.astype(np.uint8), axis=-1, bitorder="little")
-
-
-def out_bytes(dt, n, Cout, P):
-    return n * Cout * {"float32": 4 * P, "float16": 2 * P, "uint8": P, "bits": (P + 7) // 8}[dt]
 
 
 def typed_expand(c, ring_d, n, F, head, kind, C, lut, dt, Cout, P, offset=0, stream=None, buf=None):
@@ -133,7 +101,7 @@ def oracle_obs(hw, F, head, mode, kind):
 @pytest.mark.parametrize("F,head", [(4, 1), (3, 0), (5, 4)])
 @pytest.mark.parametrize("hw", SIZES)
 def test_typed_expansion_matches_oracle(hw, F, head):
-    c = Ctx(hw)
+    c = obs_world(hw)
     P = hw[0] * hw[1]
     ring_h = seeded_ring(hw, F, 1000 * hw[0] + 10 * F + head)
     for n in (1, N_MAX):
@@ -160,7 +128,7 @@ def test_typed_expansion_matches_oracle(hw, F, head):
 @pytest.mark.parametrize("hw", [(8, 12), (128, 128)])
 def test_typed_expansion_into_unaligned_output(hw):
     """An output or a ring that is not 16-byte aligned takes the byte-granular kernels."""
-    c = Ctx(hw)
+    c = obs_world(hw)
     F, head, mode, P = 4, 1, "6-class", hw[0] * hw[1]
     n = N_MAX if P < 1000 else 2
     ring_d = torch.from_numpy(np.ascontiguousarray(seeded_ring(hw, F, 1000 * hw[0] + 10 * F + head)[:, :n])).cuda()
@@ -205,7 +173,7 @@ def expected_f32(ring_h, head, kind, C, lut):
 
 @pytest.mark.parametrize("hw", [(9, 8), (128, 128)])
 def test_typed_equals_float32_expansion_with_off_palette_ids(hw):
-    c = Ctx(hw)
+    c = obs_world(hw)
     F, head, n, P = 4, 2, 3, hw[0] * hw[1]
     ring_h = np.ascontiguousarray(seeded_ring(hw, F, 77, off_palette=True)[:, :n])
     assert (ring_h == OP.OFF_PALETTE).any()
@@ -239,7 +207,7 @@ def test_typed_equals_float32_expansion_with_off_palette_ids(hw):
 @pytest.mark.parametrize("pixels", [35, 96, 16384])
 @pytest.mark.parametrize("rows", [1, 7, 216])
 def test_unpack_obs_matches_reference(rows, pixels):
-    c = Ctx()
+    c = obs_world()
     rng = np.random.default_rng(rows * 31 + pixels)
     nb = (pixels + 7) // 8
     packed_h = rng.integers(0, 256, (rows, nb), dtype=np.uint8)
@@ -266,7 +234,7 @@ def test_unpack_obs_matches_reference(rows, pixels):
 
 # ------------------------------------------------------------ 4. refusals
 def test_typed_expansion_refusals_leave_the_output_untouched():
-    c = Ctx()
+    c = obs_world()
     n, F = 2, 4
     ring = torch.zeros((F, n, 128, 128), dtype=torch.uint8, device="cuda")
     out = torch.full((n * 24 * 128 * 128 * 4,), 0xA5, dtype=torch.uint8, device="cuda")
@@ -392,7 +360,7 @@ def test_typed_expansion_under_graph_capture(dt, kind):
     """cbev_expand_obs_typed allocates nothing: captured once, each replay expands
     the ring as it is at replay time."""
     hw, F, head, n, mode = (128, 128), 4, 1, 3, "6-class"
-    c = Ctx(hw)
+    c = obs_world(hw)
     P, Cout, lut = hw[0] * hw[1], cout(kind, F, 6), semantic_lut(mode)
     order = [(head + 1 + f) % F for f in range(F)]
     rings = [np.ascontiguousarray(seeded_ring(hw, F, s)[:, :n]) for s in (21, 22)]

@@ -21,231 +21,13 @@ from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import check, lib
 from carlabev_env_amd.semantics import gray_lut, rgb_lut, semantic_lut, rgb_to_semantic_mask_ids, PALETTE
 from carlabev_env_amd.config import RandomNavigationReset, build_random_navigation_options
+from gpu_harness import (KEYS, P_, DevWorld, EpisodeStatsOn, bank_cursor, error_flags, flush_all, make_lane, out_bufs,
+                         ptr, reset_counts, reset_rows, same_records, same_stats)
+from gpu_scenes import (cached_bank_frames_match_render, compare_records, deferred_pair, edge_states, info_of,
+                        run_parity)
 from helpers import CAPS_FULL, action_stream, bench_caps, build_records, world
 
 pytestmark = pytest.mark.gpu
-
-P_ = ctypes.c_void_p
-
-
-def ptr(t):
-    return P_(t.data_ptr()) if t is not None else None
-
-
-class DevWorld:
-    def __init__(self, P, padded, caps):
-        L = lib()
-        LY.check_library_layout(L, caps)  # records are packed with the header's layout
-        self.ctx = P_()
-        check(L.cbev_create(ctypes.byref(P), ctypes.byref(caps.c()), 0, ctypes.byref(self.ctx)), "create")
-        check(L.cbev_set_map(self.ctx, padded.ctypes.data_as(P_), padded.nbytes), "set_map")
-
-    def __del__(self):
-        lib().cbev_destroy(self.ctx)
-
-
-def angles_close(a, b, tol=1e-9):
-    """Headings equal modulo 2 pi. A retreat's rebuilt route is np.unwrap'ed: where a
-    segment heading sits on the +-pi cut, ulp-level differences in the smoothed
-    route (device Savitzky-Golay tables vs the oracle's long-double fit, device vs
-    glibc sin/cos in the actor's position) can flip atan2's sign there and offset
-    every later heading by exactly 2 pi, which angle_mod and cos/sin absorb."""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    d = np.remainder(a - b + np.pi, 2 * np.pi) - np.pi
-    return bool(np.all(np.abs(d) <= tol * (1 + np.abs(b))))
-
-
-def compare_records(a: np.ndarray, b: np.ndarray, layout, tag=""):
-    va, vb = LY.RecordView(a, layout), LY.RecordView(b, layout)
-    ints = ("TIDX", "NROUTE", "NACT", "TILE", "COLLIDED", "ACTOR_ID", "CAUSE", "TERM", "TRUNC", "EP_LEN",
-            "HAS_PREV_COMFORT", "S_PREV_VALID", "KSTEPS", "OFFROAD", "NACTSTATE")
-    for k in ints:
-        assert va.i(k) == vb.i(k), (tag, k, va.i(k), vb.i(k))
-    assert np.array_equal(va.vis, vb.vis), (tag, "vis")
-    assert np.array_equal(va.vis_draw, vb.vis_draw), (tag, "vis_draw")
-    assert np.allclose(va.hd, vb.hd, rtol=1e-9, atol=1e-9, equal_nan=True), (
-        tag, [(n, va.hd[i], vb.hd[i]) for n, i in LY.HD.items()
-              if not np.isclose(va.hd[i], vb.hd[i], rtol=1e-9, atol=1e-9, equal_nan=True)])
-    n = va.i("NACT")
-    assert np.array_equal(va.ai[:, :n], vb.ai[:, :n]), (tag, "actor ints")
-    yaw = LY.AD["YAW"]
-    rows = [i for i in range(va.ad.shape[0]) if i != yaw]
-    assert np.allclose(va.ad[rows, :n], vb.ad[rows, :n], rtol=1e-9, atol=1e-9), (tag, "actor doubles")
-    assert angles_close(va.ad[yaw, :n], vb.ad[yaw, :n]), (tag, "actor yaw")
-    for a in range(n):  # actor routes (rebuilt on a jaywalk retreat): smoothed up to NROUTE, raw up to NRX
-        m, k = va.ai[LY.AI["NROUTE"], a], va.ai[LY.AI["NRX"], a]
-        for arr in ("acx", "acy", "arx", "ary"):
-            mk = k if arr in ("arx", "ary") else m
-            assert np.allclose(getattr(va, arr)[a, :mk], getattr(vb, arr)[a, :mk], rtol=1e-9, atol=1e-9), (tag, arr, a)
-        assert angles_close(va.acyaw[a, :m], vb.acyaw[a, :m]), (tag, "acyaw", a)
-        # a: the device record; its float32 route copy (the target search's first
-        # pass) follows every rebuild of the smoothed route
-        assert np.array_equal(va.acf[a, :m, 0], va.acx[a, :m].astype(np.float32)), (tag, "acf x", a)
-        assert np.array_equal(va.acf[a, :m, 1], va.acy[a, :m].astype(np.float32)), (tag, "acf y", a)
-        # and its pruning circles (acb) hold every block's float32 points
-        assert acb_holds(va.acb[a], va.acf[a, :m]), (tag, "acb", a)
-
-
-def acb_holds(acb, pts) -> bool:
-    """Every float32 route point lies inside its block's circle (cbev_layout.h acb)."""
-    P = LY.ACB_PTS
-    for b in range((len(pts) + P - 1) // P):
-        w0, w1 = int(acb[b, 0]), int(acb[b, 1])
-        c = np.array([(w0 & 0xFFFF) - 32768, (w0 >> 16) - 32768], np.float64) / 8.0
-        q = pts[P * b: P * (b + 1)].astype(np.float64)
-        if np.hypot(q[:, 0] - c[0], q[:, 1] - c[1]).max() > w1 / 8.0:
-            return False
-    return True
-
-
-def info_of(v, cause):
-    """The per-step export cbev_step writes to `info` (include/cbev.h), from an oracle record."""
-    o = np.zeros(16, np.float32)
-    o[0:7] = v.hd[LY.HD["C_SPEED"]:LY.HD["C_SPEED"] + 7]
-    o[7:11] = v.hd[LY.HD["U_GAS"]:LY.HD["U_GAS"] + 4]
-    o[11] = v.h("REWARD")
-    o[12] = v.h("DIST2WP")
-    o[13] = v.i("TILE")
-    o[14] = v.i("COLLIDED")
-    o[15] = v.i("NACTSTATE")
-    return o
-
-
-class EpisodeStatsOn:
-    """The device episode statistics (cbev_set_episode_stats) on a context, as
-    the bench's info_mode "full" runs the step: k_ego then updates the per-env
-    Stats accumulators and writes a summary row per termination (the kernel
-    variant the headline measures). `check(step, term, sample, views, causes)`
-    compares this step's rows with the oracle's records of the sampled envs."""
-    RING = 4
-
-    def __init__(self, ctx, n):
-        self.n = n
-        self.stats = torch.zeros((n, LY.STATS_BYTES), dtype=torch.uint8, device="cuda")
-        self.rows = torch.zeros((self.RING, n, len(LY.EP)), dtype=torch.float64, device="cuda")
-        self.counts = torch.zeros(self.RING, dtype=torch.int32, device="cuda")
-        check(lib().cbev_set_episode_stats(ctx, ptr(self.stats), n, ptr(self.rows), ptr(self.counts), self.RING),
-              "episode_stats")
-        self.episodes = np.zeros(n, np.int64)
-        self.rows_seen = 0
-
-    def check(self, step, term_all, sample, views, causes):
-        slot = step % self.RING
-        cnt = int(self.counts[slot].item())
-        assert cnt == int(term_all.sum()), (step, cnt, int(term_all.sum()))
-        rows = self.rows[slot, :cnt].cpu().numpy()
-        by_env = {int(r[LY.EP["ENV"]]): r for r in rows}
-        assert len(by_env) == cnt, (step, "one row per terminated env")
-        for j, e in enumerate(sample):
-            v = views[j]
-            if not v.i("TERM"):
-                assert e not in by_env, (step, e)
-                continue
-            r = by_env[int(e)]
-            assert r[LY.EP["CAUSE"]] == causes[j] == v.i("CAUSE"), (step, e)
-            assert r[LY.EP["EPISODE"]] == self.episodes[e], (step, e)
-            assert r[LY.EP["LENGTH"]] == v.i("EP_LEN"), (step, e)
-            assert np.isclose(r[LY.EP["RETURN"]], v.h("EP_RETURN"), rtol=1e-9, atol=1e-12), (step, e)
-            ln = max(v.i("EP_LEN"), 1)
-            assert np.isclose(r[LY.EP["MEAN_SPEED"]], v.h("EP_SPEED") / ln, rtol=1e-9, atol=1e-12), (step, e)
-            self.rows_seen += 1
-        for e in np.flatnonzero(term_all):
-            self.episodes[e] += 1
-
-
-def error_flags(ctx):
-    f = ctypes.c_int32()
-    check(lib().cbev_error_flags(ctx, ctypes.byref(f), 1), "error_flags")
-    return f.value
-
-
-def run_parity(kinds, n_envs, steps, size=128, profile="discrete9_v1", reward="carl_base_v1", seed0=0, anchor_y=0.5,
-               act_seed=1234, edit=None, fov=False, caps=CAPS_FULL, options=None, acts=None, on_step=None,
-               stats=False, recs=None, world_=None):
-    """Every env of a small batch stepped on the device and by the oracle, compared
-    whole after each step. recs (with world_ = (P, padded map) and caps): authored
-    records (tests/edge_cases.py) instead of the scene builder's; acts: an
-    explicit (steps, n[, 3]) action array instead of the seeded stream; on_step(t, views, causes): sees the oracle's records after
-    each step (branch-coverage probes); stats: with the device episode statistics
-    on (EpisodeStatsOn), the headline's k_ego variant."""
-    if recs is not None:  # authored records: no scene generator (size 64 has none that works)
-        P, padded = world_
-        layout = LY.Layout.make(caps)
-        recs = recs.copy()
-        assert recs.shape == (n_envs, layout.record_bytes) and edit is None
-    else:
-        cfg, P, padded, layout, builder = world(size, profile, reward, anchor_y, caps=caps)
-        if options is None:
-            recs, _ = build_records(builder, n_envs, kinds, seed0=seed0)
-        else:  # explicit scene options (e.g. more vehicles than the difficulty presets)
-            recs, _ = builder.build_many([seed0 + i for i in range(n_envs)],
-                                         lambda k, s: dict(options[k % len(options)], scene_seed=s))
-    if edit is not None:  # hand-made states on top of the seeded scenes
-        edit(recs, layout, P)
-    dw = DevWorld(P, padded, caps)
-    L = lib()
-    S = P.size
-    omask = None
-    if fov:  # device: the product's mask; oracle: its own restatement, blacked out after the render
-        import wrappers as W
-        from carlabev_env_amd.fov_mask import fov_corner_mask
-        dmask = fov_corner_mask(S)
-        check(L.cbev_set_fov_mask(dw.ctx, dmask.ctypes.data_as(P_)), "fov")
-        omask = W.fov_mask(S)
-    d_recs = torch.from_numpy(recs.copy()).cuda()
-    d_frames = torch.zeros((n_envs, S, S), dtype=torch.uint8, device="cuda")
-    check(L.cbev_reset(dw.ctx, ptr(d_recs), n_envs, None, 0, None, None, 0, ptr(d_frames), 1, None), "reset")
-    orc = O.Oracle(P, padded, caps.c(), layout.record_bytes)
-    h_frames = np.zeros((n_envs, S, S), np.uint8)
-    for e in range(n_envs):
-        orc.reset_obs(recs[e], h_frames[e])
-        if omask is not None:
-            h_frames[e][omask] = 8  # CBEV_PX_BLACK
-    torch.cuda.synchronize()
-    assert np.array_equal(d_frames.cpu().numpy(), h_frames), "reset frames differ"
-    if acts is None:
-        acts = action_stream(P, n_envs, steps, seed=act_seed)
-    st = EpisodeStatsOn(dw.ctx, n_envs) if stats else None
-    rew = torch.zeros(n_envs, dtype=torch.float64, device="cuda")
-    term = torch.zeros(n_envs, dtype=torch.uint8, device="cuda")
-    trunc = torch.zeros_like(term)
-    cause = torch.zeros(n_envs, dtype=torch.int32, device="cuda")
-    info = torch.zeros((n_envs, 16), dtype=torch.float32, device="cuda")
-    n_term = 0
-    for t in range(steps):
-        a = torch.from_numpy(np.ascontiguousarray(acts[t])).cuda()
-        check(L.cbev_step(dw.ctx, ptr(d_recs), n_envs, ptr(a), ptr(d_frames), ptr(rew), ptr(term), ptr(trunc),
-                          ptr(cause), ptr(info), None), "step")
-        h_cause = np.zeros(n_envs, np.int32)
-        for e in range(n_envs):
-            h_cause[e] = orc.step_one(recs[e], np.ascontiguousarray(acts[t, e]), h_frames[e])
-            if omask is not None:
-                h_frames[e][omask] = 8  # CBEV_PX_BLACK
-        torch.cuda.synchronize()
-        df = d_frames.cpu().numpy()
-        bad = np.argwhere(df != h_frames)
-        assert bad.size == 0, (t, bad[:8], df[tuple(bad[0])], h_frames[tuple(bad[0])])
-        dr = d_recs.cpu().numpy()
-        for e in range(n_envs):
-            compare_records(dr[e], recs[e], layout, tag=(t, e))
-        views = [LY.RecordView(recs[e], layout) for e in range(n_envs)]
-        assert np.array_equal(term.cpu().numpy(), np.array([v.i("TERM") for v in views], np.uint8))
-        assert np.array_equal(trunc.cpu().numpy(), np.array([v.i("TRUNC") for v in views], np.uint8))
-        assert np.allclose(rew.cpu().numpy(), [v.h("REWARD") for v in views], rtol=1e-9, atol=1e-12)
-        # this step's cause (not the record's sticky last non-None cause) and the per-step export
-        assert np.array_equal(cause.cpu().numpy(), h_cause), (t, cause.cpu().numpy(), h_cause)
-        want = np.stack([info_of(v, h_cause[e]) for e, v in enumerate(views)])
-        got = info.cpu().numpy()
-        assert np.array_equal(got[:, 13:], want[:, 13:]), (t, "info ints")
-        assert np.allclose(got, want, rtol=1e-6, atol=1e-6), (t, "info")
-        if st is not None:
-            st.check(t, term.cpu().numpy(), np.arange(n_envs), views, h_cause)
-        if on_step is not None:
-            on_step(t, views, h_cause)
-        n_term += int(term.sum())
-    # no raster tile exceeded its LDS window bound (CBEV_ERR_RASTER_WINDOW), no bad action index
-    assert error_flags(dw.ctx) == 0
-    return n_term
 
 
 def test_parity_ego_only_config2():
@@ -281,29 +63,13 @@ def test_parity_shaping_reward_and_offcentre_anchor():
     run_parity(["rt_easy_v1", "jaywalk"], 16, 80, reward="shaping_base_v1", anchor_y=0.2, seed0=5)
 
 
-def _edge_states(recs, layout, P):
-    """One env per branch the seeded rollouts rarely reach."""
-    V = [LY.RecordView(recs[e], layout) for e in range(recs.shape[0])]
-    X, Y, YAW, VEL = (LY.HD[k] for k in ("X", "Y", "YAW", "V"))
-    V[1].hd[X] += 40.0  # off the road: NON_DRIVABLE tile (collision) or sidewalk
-    V[2].hd[X], V[2].hd[Y] = V[2].hd[LY.HD["GOAL_X"]], V[2].hd[LY.HD["GOAL_Y"]]  # on the goal: success
-    V[3].hd[X] += 120.0  # far from the route: out of bounds or off-road
-    V[4].hd[VEL] = 60.0  # over the CaRL speed limit, brake/clip paths
-    if V[5].i("NACT") > 0:  # on an actor: vehicle / pedestrian collision
-        V[5].hd[X], V[5].hd[Y] = V[5].ad[LY.AD["X"], 0], V[5].ad[LY.AD["Y"], 0]
-    V[6].hd[YAW], V[6].hd[VEL] = -np.pi / 2, 0.0  # exact multiple of 90 degrees: rotate90 in the step raster
-    V[7].hd[YAW] = np.pi  # yaw at the angle_mod wrap
-    V[8].hd[VEL] = -3.0  # reversing
-    V[9].hd[X] = 3.0  # at the map's left edge: crop clamped against the padding
-
-
 def test_parity_edge_states_carl():
-    run_parity(["rt_medium_v1"], 10, 6, seed0=777, edit=_edge_states)
+    run_parity(["rt_medium_v1"], 10, 6, seed0=777, edit=edge_states)
 
 
 def test_parity_edge_states_shaping_and_truncation():
     def edit(recs, layout, P):
-        _edge_states(recs, layout, P)
+        edge_states(recs, layout, P)
         LY.RecordView(recs[0], layout).hi[LY.HI["KSTEPS"]] = P.max_actions - 2  # truncation on step 2
     run_parity(["rt_easy_v1"], 10, 4, reward="shaping_base_v1", seed0=4242, edit=edit)
 
@@ -395,45 +161,10 @@ def test_reset_from_cached_bank_frames_matches_render():
     n, B, F = 48, 9, 4
     recs, _ = build_records(builder, n, ["rt_medium_v1"], seed0=1300)
     bank, _ = build_records(builder, B, ["rt_hard_v1", "jaywalk", "lead_brake"], seed0=1900)
-    _cached_bank_frames_match_render(P, padded, CAPS_FULL, recs, bank, F)
+    cached_bank_frames_match_render(P, padded, CAPS_FULL, recs, bank, F)
     # size 64 (k_bank_frames<1>, k_reset<1> into a 4-slot ring), authored records
     P, padded, caps, recs = _authored64(n)
-    _cached_bank_frames_match_render(P, padded, caps, recs, _authored64(B, first=7)[3], F)
-
-
-def _cached_bank_frames_match_render(P, padded, caps, recs, bank, F):
-    n, B = len(recs), len(bank)
-    dw = DevWorld(P, padded, caps)
-    L = lib()
-    S = P.size
-    d_bank = torch.from_numpy(bank.copy()).cuda()
-    mask = (torch.arange(n) % 4 != 1).to(torch.uint8).cuda()
-    bidx = ((torch.arange(n) * 7) % B).to(torch.int32).cuda()
-    outs = []
-    for cached in (False, True):
-        d_recs = torch.from_numpy(recs.copy()).cuda()
-        ring = torch.full((F, n, S, S), 13, dtype=torch.uint8, device="cuda")
-        for idx, off in ((bidx, 0), (None, 5)):
-            if cached:
-                bf = torch.zeros((B, S, S), dtype=torch.uint8, device="cuda")
-                check(L.cbev_bank_frames(dw.ctx, ptr(d_bank), B, ptr(bf), None), "bank_frames")
-                check(L.cbev_reset_frames(dw.ctx, ptr(d_recs), n, ptr(d_bank), B, ptr(mask), ptr(idx), off, ptr(bf),
-                                          ptr(ring), F, None), "reset_frames")
-            else:
-                check(L.cbev_reset(dw.ctx, ptr(d_recs), n, ptr(d_bank), B, ptr(mask), ptr(idx), off, ptr(ring), F,
-                                   None), "reset")
-        torch.cuda.synchronize()
-        outs.append((d_recs.cpu().numpy(), ring.cpu().numpy()))
-    assert np.array_equal(outs[0][0], outs[1][0])
-    assert np.array_equal(outs[0][1], outs[1][1])
-    # and the ring of a reset env is the oracle's reset frame of its bank row (second call: b = (e + 5) % B)
-    orc = O.Oracle(P, padded, caps.c(), LY.Layout.make(caps).record_bytes)
-    f = np.zeros((S, S), np.uint8)
-    for e in range(0, n, 5):
-        if e % 4 != 1:
-            orc.reset_obs(bank[(e + 5) % B].copy(), f)
-            for s in range(F):
-                assert np.array_equal(outs[1][1][s, e], f), (S, e, s)
+    cached_bank_frames_match_render(P, padded, caps, recs, _authored64(B, first=7)[3], F)
 
 
 def test_vector_env_surface_and_partial_reset():
@@ -601,11 +332,7 @@ def run_full_size(kinds, n_envs, size=128, profile="discrete9_v1", seed0=0, step
     orc = O.Oracle(P, padded, caps.c(), layout.record_bytes)
     h_recs = recs[sample].copy()
     h_frames = np.zeros((len(sample), S, S), np.uint8)
-    rew = torch.zeros(n_envs, dtype=torch.float64, device="cuda")
-    term = torch.zeros(n_envs, dtype=torch.uint8, device="cuda")
-    trunc = torch.zeros_like(term)
-    cause = torch.zeros(n_envs, dtype=torch.int32, device="cuda")
-    info = torch.zeros((n_envs, 16), dtype=torch.float32, device="cuda")
+    rew, term, trunc, cause, info = out_bufs(n_envs).values()
     st = EpisodeStatsOn(dw.ctx, n_envs) if stats else None
     prng = np.random.default_rng(act_seed + 1)
     pos = {int(e): j for j, e in enumerate(sample)}
@@ -685,16 +412,10 @@ def run_full_size_folded(n_envs, steps, caps, seed0, bank_seed0, act_seed=1, dis
     bank = bdist[np.arange(n_bank) % bank_distinct].copy()
     for b in range(0, n_bank, 3):
         LY.RecordView(bank[b], layout).hd[LY.HD["X"]] += 60.0
-    dw = DevWorld(P, padded, caps)
+    dw, d_bank, bf, d_recs, ring, b = make_lane(P, padded, caps, recs, bank, F, deferred=1)
+    rew, term, trunc, cause, info, st = b.values()
     L = lib()
     S = P.size
-    check(L.cbev_set_deferred_reset(dw.ctx, 1), "deferred")
-    d_bank = torch.from_numpy(bank).cuda()
-    bf = torch.zeros((n_bank, S, S), dtype=torch.uint8, device="cuda")
-    check(L.cbev_bank_frames(dw.ctx, ptr(d_bank), n_bank, ptr(bf), None), "bank_frames")
-    d_recs = torch.from_numpy(recs).cuda()
-    ring = torch.zeros((F, n_envs, S, S), dtype=torch.uint8, device="cuda")
-    check(L.cbev_reset(dw.ctx, ptr(d_recs), n_envs, None, 0, None, None, 0, ptr(ring), F, None), "reset")
     orc = O.Oracle(P, padded, caps.c(), layout.record_bytes)
     sample = _sample_envs(n_envs)
     pos = {int(e): j for j, e in enumerate(sample)}
@@ -717,12 +438,6 @@ def run_full_size_folded(n_envs, steps, caps, seed0, bank_seed0, act_seed=1, dis
     p[1] += 4.0
     acts = rng.choice(P.n_discrete, size=(steps, n_envs), p=p / p.sum()).astype(np.int32)
     prng = np.random.default_rng(act_seed + 1)
-    rew = torch.zeros(n_envs, dtype=torch.float64, device="cuda")
-    term = torch.zeros(n_envs, dtype=torch.uint8, device="cuda")
-    trunc = torch.zeros_like(term)
-    cause = torch.zeros(n_envs, dtype=torch.int32, device="cuda")
-    info = torch.zeros((n_envs, 16), dtype=torch.float32, device="cuda")
-    st = EpisodeStatsOn(dw.ctx, n_envs)
     seq = np.zeros(n_envs, np.int64)
     pending = None
     folded = flushed = reset_then_term = resets_seen = 0
@@ -785,7 +500,7 @@ def run_full_size_folded(n_envs, steps, caps, seed0, bank_seed0, act_seed=1, dis
         check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n_envs, ptr(d_bank), n_bank, ptr(bf), ptr(ring), F, None),
               "reset_terminated")
     check(L.cbev_flush(dw.ctx), "flush")
-    assert np.array_equal(_counts(L, dw, n_envs), seq)
+    assert np.array_equal(reset_counts(L, dw, n_envs), seq)
     assert error_flags(dw.ctx) == 0
     if caps.actor_cap == 0:  # the fold (k_ego) needs a context without actor slots
         assert folded >= steps // 2 and flushed >= 2, (folded, flushed)
@@ -894,26 +609,7 @@ def _bank_world(n, B, F, caps, kinds, seed0, bank_seed0):
     cfg, P, padded, layout, builder = world(caps=caps)
     recs, _ = build_records(builder, n, kinds, seed0=seed0)
     bank, _ = build_records(builder, B, kinds, seed0=bank_seed0)
-    dw = DevWorld(P, padded, caps)
-    L = lib()
-    S = P.size
-    d_bank = torch.from_numpy(bank.copy()).cuda()
-    bf = torch.zeros((B, S, S), dtype=torch.uint8, device="cuda")
-    check(L.cbev_bank_frames(dw.ctx, ptr(d_bank), B, ptr(bf), None), "bank_frames")
-    d_recs = torch.from_numpy(recs.copy()).cuda()
-    ring = torch.zeros((F, n, S, S), dtype=torch.uint8, device="cuda")
-    check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), F, None), "reset")
-    return P, layout, dw, d_bank, bf, d_recs, ring
-
-
-def reset_rows(mask_np, tcount, B):
-    """The bank rows a masked reset hands out (include/cbev.h, ABI 7): env e takes
-    (e + j * cbev_bank_stride(B)) % B, j = tcount[e], its terminations so far
-    (counted by the steps)."""
-    ids = np.flatnonzero(mask_np)
-    stride = lib().cbev_bank_stride(B)
-    rows = (ids.astype(np.int64) + tcount[ids].astype(np.int64) * stride) % B
-    return ids, rows
+    return P, layout, make_lane(P, padded, caps, recs, bank, F, stats=False)
 
 
 def _want_reset(L, dw, d_recs, ring, d_bank, bf, mask_np, tcount, F):
@@ -929,31 +625,16 @@ def _want_reset(L, dw, d_recs, ring, d_bank, bf, mask_np, tcount, F):
     return want_r, want_f, len(ids)
 
 
-def _cursor(L, dw):
-    c = ctypes.c_int64()
-    check(L.cbev_bank_cursor(dw.ctx, ctypes.byref(c)), "cursor")
-    return c.value
-
-
-def _counts(L, dw, n):
-    out = np.zeros(n, np.uint32)
-    check(L.cbev_reset_counts(dw.ctx, out.ctypes.data_as(P_), n), "reset_counts")
-    return out
-
-
 def test_reset_terminated_matches_masked_reset():
     """cbev_reset_terminated (the canonical loop's reset from the last step's term
     buffer) = cbev_reset_frames with mask = that step's terminations and the bank
     rows of the per-env rule (reset_rows: env e takes (e + j * stride) % B after
     its j-th termination); each step counts its terminations."""
     n, B, F = 45, 11, 4
-    P, layout, dw, d_bank, bf, d_recs, ring = _bank_world(n, B, F, bench_caps(3), ["rt_hard_v1", "rt_medium_v1"],
-                                                           2100, 2900)
+    P, layout, lane = _bank_world(n, B, F, bench_caps(3), ["rt_hard_v1", "rt_medium_v1"], 2100, 2900)
+    dw, d_bank, bf, d_recs, ring, b = lane
+    rew, term, trunc, cause = (b[k] for k in KEYS[:4])
     L = lib()
-    rew = torch.zeros(n, dtype=torch.float64, device="cuda")
-    term = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    trunc = torch.zeros_like(term)
-    cause = torch.zeros(n, dtype=torch.int32, device="cuda")
     acts = action_stream(P, n, 12, seed=7)
     seq = np.zeros(n, np.int64)
     rng = np.random.default_rng(5)
@@ -970,14 +651,14 @@ def test_reset_terminated_matches_masked_reset():
         torch.cuda.synchronize()
         tn = term.cpu().numpy().astype(bool)
         seq += tn
-        assert np.array_equal(_counts(L, dw, n), seq), t
+        assert np.array_equal(reset_counts(L, dw, n), seq), t
         want_r, want_f, k = _want_reset(L, dw, d_recs, ring, d_bank, bf, tn, seq, F)
         total += k
         check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n, ptr(d_bank), B, ptr(bf), ptr(ring), F, None), "reset_term")
         torch.cuda.synchronize()
         assert torch.equal(d_recs, want_r), t
         assert torch.equal(ring, want_f), t
-        assert _cursor(L, dw) == total, t
+        assert bank_cursor(L, dw) == total, t
     assert total > 20 and seq.max() >= 2  # some env walked past its first bank row
     # n must match the last step's
     assert L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n - 1, ptr(d_bank), B, ptr(bf), ptr(ring), F, None) != 0
@@ -990,12 +671,10 @@ def test_reset_masked_mass_termination_and_edits():
     the reset reads the buffer when it runs), an unaligned mask view, and a step
     with no reset (the cursor moves only when a reset runs)."""
     n, B, F = 4099, 5003, 1
-    P, layout, dw, d_bank, bf, d_recs, ring = _bank_world(n, B, F, bench_caps(2), ["rt_no_traffic_v1"], 6000, 16000)
+    P, layout, lane = _bank_world(n, B, F, bench_caps(2), ["rt_no_traffic_v1"], 6000, 16000)
+    dw, d_bank, bf, d_recs, ring, b = lane
+    rew, term, trunc, cause = (b[k] for k in KEYS[:4])
     L = lib()
-    rew = torch.zeros(n, dtype=torch.float64, device="cuda")
-    term = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    trunc = torch.zeros_like(term)
-    cause = torch.zeros(n, dtype=torch.int32, device="cuda")
     acts = action_stream(P, n, 6, seed=3)
     rng = np.random.default_rng(11)
     seq = np.zeros(n, np.int64)
@@ -1019,10 +698,10 @@ def test_reset_masked_mass_termination_and_edits():
     check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n, ptr(d_bank), B, ptr(bf), ptr(ring), F, None), "reset_term")
     torch.cuda.synchronize()
     assert torch.equal(d_recs, want_r) and torch.equal(ring, want_f)
-    assert _cursor(L, dw) == seq.sum()
+    assert bank_cursor(L, dw) == seq.sum()
     # 2: a step whose terminations are not reset: they are counted all the same
     step(1, rng.choice(n, size=300, replace=False))
-    assert term.cpu().numpy().sum() > 0 and np.array_equal(_counts(L, dw, n), seq)
+    assert term.cpu().numpy().sum() > 0 and np.array_equal(reset_counts(L, dw, n), seq)
     # 3: in-place edits of the term buffer before the reset
     step(2, rng.choice(n, size=700, replace=False))
     extra = torch.from_numpy((rng.random(n) < 0.05).astype(np.uint8)).cuda()
@@ -1033,7 +712,7 @@ def test_reset_masked_mass_termination_and_edits():
     check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n, ptr(d_bank), B, ptr(bf), ptr(ring), F, None), "reset_term")
     torch.cuda.synchronize()
     assert torch.equal(d_recs, want_r) and torch.equal(ring, want_f)
-    assert np.array_equal(_counts(L, dw, n), seq)
+    assert np.array_equal(reset_counts(L, dw, n), seq)
     # 4: cbev_reset_masked with an arbitrary mask at an odd byte offset (byte-wise mask loads)
     buf = torch.zeros(n + 3, dtype=torch.uint8, device="cuda")
     mview = buf[3:]
@@ -1054,7 +733,7 @@ def test_reset_masked_mass_termination_and_edits():
           "reset_masked again")
     torch.cuda.synchronize()
     assert torch.equal(d_recs, want_r) and torch.equal(ring, want_f)
-    assert np.array_equal(_counts(L, dw, n), seq) and _cursor(L, dw) == seq.sum()
+    assert np.array_equal(reset_counts(L, dw, n), seq) and bank_cursor(L, dw) == seq.sum()
 
 
 def test_reset_cursor_advances_under_graph_replay():
@@ -1063,13 +742,11 @@ def test_reset_cursor_advances_under_graph_replay():
     env's next row after each new termination (each replay = the eager calls,
     reset_rows), the steps inside the graph counting the terminations."""
     n, B, F = 45, 17, 2
-    P, layout, dw, d_bank, bf, d_recs, ring = _bank_world(n, B, F, bench_caps(2), ["rt_no_traffic_v1"], 3100, 3900)
+    P, layout, lane = _bank_world(n, B, F, bench_caps(2), ["rt_no_traffic_v1"], 3100, 3900)
+    dw, d_bank, bf, d_recs, ring, b = lane
+    rew, term, trunc, cause = (b[k] for k in KEYS[:4])
     L = lib()
-    rew = torch.zeros(n, dtype=torch.float64, device="cuda")
-    term = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    trunc = torch.zeros_like(term)
-    cause = torch.zeros(n, dtype=torch.int32, device="cuda")
-    a = torch.zeros(n, dtype=torch.int32, device="cuda")
+    a =torch.zeros(n, dtype=torch.int32, device="cuda")
     check(L.cbev_step(dw.ctx, ptr(d_recs), n, ptr(a), ptr(ring[0]), ptr(rew), ptr(term), ptr(trunc), ptr(cause),
                       None, None), "step")
     torch.cuda.synchronize()
@@ -1082,7 +759,7 @@ def test_reset_cursor_advances_under_graph_replay():
             check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n, ptr(d_bank), B, ptr(bf), ptr(ring), F,
                                           P_(torch.cuda.current_stream().cuda_stream)), "reset_term (capture)")
     torch.cuda.synchronize()
-    seq = _counts(L, dw, n).astype(np.int64)  # capture runs nothing
+    seq = reset_counts(L, dw, n).astype(np.int64)  # capture runs nothing
     total = 0
     for rep in range(4):
         h = d_recs.cpu().numpy()  # push the selected envs off the road: the next step terminates them
@@ -1094,76 +771,13 @@ def test_reset_cursor_advances_under_graph_replay():
         torch.cuda.synchronize()
         tn = term.cpu().numpy().astype(bool)
         seq += tn
-        assert np.array_equal(_counts(L, dw, n), seq), rep
+        assert np.array_equal(reset_counts(L, dw, n), seq), rep
         want_r, want_f, k = _want_reset(L, dw, d_recs, ring, d_bank, bf, tn, seq, F)
         g.replay()
         torch.cuda.synchronize()
         assert torch.equal(d_recs, want_r) and torch.equal(ring, want_f), rep
         total += k
     assert total >= 8 and seq.max() >= 3
-
-
-def _same_records(a, b, layout):
-    """Records equal but for RS_FAST's bits above bit 0 (device scratch: a folded
-    reset's bank row for k_raster, k_ego -> k_raster of one step)."""
-    o = layout.off["hi"] + 4 * LY.HI["RS_FAST"]
-    a, b = a.clone(), b.clone()
-    for r in (a, b):
-        v = r.view(r.shape[0], -1)[:, o:o + 4].contiguous().view(torch.int32) & 1
-        r.view(r.shape[0], -1)[:, o:o + 4] = v.view(torch.uint8).view(r.shape[0], 4)
-    return torch.equal(a, b)
-
-
-def _deferred_pair(n, B, F, caps, seed0, bank_seed0, stats=True):
-    """Two contexts on the same scenes and bank: reset_terminated launched at once
-    (A) and deferred into the next step (B, cbev_set_deferred_reset); with the
-    device episode statistics on in both (stats: the headline's k_ego variant)."""
-    cfg, P, padded, layout, builder = world(caps=caps)
-    recs, _ = build_records(builder, n, ["rt_no_traffic_v1"], seed0=seed0)
-    bank, _ = build_records(builder, B, ["rt_no_traffic_v1"], seed0=bank_seed0)
-    L = lib()
-    S = P.size
-    out = []
-    for deferred in (0, 1):
-        dw = DevWorld(P, padded, caps)
-        check(L.cbev_set_deferred_reset(dw.ctx, deferred), "deferred")
-        d_bank = torch.from_numpy(bank.copy()).cuda()
-        bf = torch.zeros((B, S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_bank_frames(dw.ctx, ptr(d_bank), B, ptr(bf), None), "bank_frames")
-        d_recs = torch.from_numpy(recs.copy()).cuda()
-        ring = torch.zeros((F, n, S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), F, None), "reset")
-        bufs = dict(rew=torch.zeros(n, dtype=torch.float64, device="cuda"),
-                    term=torch.zeros(n, dtype=torch.uint8, device="cuda"),
-                    trunc=torch.zeros(n, dtype=torch.uint8, device="cuda"),
-                    cause=torch.zeros(n, dtype=torch.int32, device="cuda"),
-                    info=torch.zeros((n, 16), dtype=torch.float32, device="cuda"))
-        if stats:
-            bufs["stats"] = EpisodeStatsOn(dw.ctx, n)
-        out.append((dw, d_bank, bf, d_recs, ring, bufs))
-    return P, layout, out
-
-
-_T0 = slice(8 * 200 + 16, 8 * 200 + 24)  # cbev_episode_stats.t0 (the device clock at the episode's reset)
-
-
-def _same_stats(a, b, step, n):
-    """The two contexts' episode statistics after `step`: per-env accumulators
-    (all but the reset clock stamp t0), this step's summary rows (by env; all
-    columns but the elapsed SECONDS) and their count."""
-    sa, sb = a.stats.cpu().numpy(), b.stats.cpu().numpy()
-    keep = np.ones(sa.shape[1], bool)
-    keep[_T0] = False
-    if not np.array_equal(sa[:, keep], sb[:, keep]):
-        return False
-    slot = step % a.RING
-    ca, cb = min(int(a.counts[slot].item()), n), min(int(b.counts[slot].item()), n)
-    if ca != cb:
-        return False
-    ra, rb_ = a.rows[slot, :ca].cpu().numpy(), b.rows[slot, :cb].cpu().numpy()
-    ra, rb_ = ra[np.argsort(ra[:, LY.EP["ENV"]])], rb_[np.argsort(rb_[:, LY.EP["ENV"]])]
-    cols = [c for c in range(ra.shape[1]) if c != LY.EP["SECONDS"]]
-    return bool(np.array_equal(ra[:, cols], rb_[:, cols]))
 
 
 def test_deferred_reset_matches_immediate():
@@ -1177,7 +791,7 @@ def test_deferred_reset_matches_immediate():
     cbev_expand_obs flushing by itself), a step with no reset before it, the frame
     ring's slots in turn, an odd batch (partial k_ego workgroup)."""
     for n, B, F in ((45, 13, 4), (4099, 6007, 4)):
-        P, layout, ctxs = _deferred_pair(n, B, F, bench_caps(2), 7000, 17000)
+        P, layout, ctxs = deferred_pair(n, B, F, bench_caps(2), 7000, 17000)
         L = lib()
         S = P.size
         acts = action_stream(P, n, 16, seed=21)
@@ -1202,9 +816,9 @@ def test_deferred_reset_matches_immediate():
             assert L.cbev_reset_pending(dB.ctx) == 0
             for k in ("rew", "term", "trunc", "cause", "info"):
                 assert torch.equal(bA[k], bB[k]), (n, t, k)
-            assert _same_stats(bA["stats"], bB["stats"], t, n), (n, t, "episode stats")
+            assert same_stats(bA["stats"], bB["stats"], t, n), (n, t, "episode stats")
             rows_seen += int(bA["stats"].counts[t % bA["stats"].RING].item())
-            assert _same_records(rA, rB, layout), (n, t, "records")
+            assert same_records(rA, rB, layout), (n, t, "records")
             assert torch.equal(gA, gB), (n, t, "ring")
             if t % 5 == 4:  # no reset before the next step
                 continue
@@ -1218,21 +832,19 @@ def test_deferred_reset_matches_immediate():
             if t % 4 == 2:  # the reset observed right away: flush
                 check(L.cbev_flush(dB.ctx), "flush")
                 torch.cuda.synchronize()
-                assert _same_records(rA, rB, layout) and torch.equal(gA, gB), (n, t, "flushed reset")
+                assert same_records(rA, rB, layout) and torch.equal(gA, gB), (n, t, "flushed reset")
             elif t % 4 == 3:  # ... or through an observation call, which flushes by itself
                 out = torch.zeros((n, S, S, 3), dtype=torch.uint8, device="cuda")
                 check(L.cbev_expand_obs(dB.ctx, ptr(gB[0][None]), n, 1, 0, 2, 3, rgb_lut().ctypes.data_as(P_),
                                         ptr(out), None), "expand")
                 torch.cuda.synchronize()
                 assert L.cbev_reset_pending(dB.ctx) == 0
-                assert _same_records(rA, rB, layout) and torch.equal(gA, gB), (n, t, "observed reset")
-        for dw, *_ in ctxs:
-            check(L.cbev_flush(dw.ctx), "flush")
-        torch.cuda.synchronize()
+                assert same_records(rA, rB, layout) and torch.equal(gA, gB), (n, t, "observed reset")
+        flush_all(ctxs)
         (dA, _, _, rA, gA, bA), (dB, _, _, rB, gB, bB) = ctxs
-        assert _same_records(rA, rB, layout) and torch.equal(gA, gB)
-        assert _cursor(L, dA) == _cursor(L, dB) and _cursor(L, dA) > 0
-        assert np.array_equal(_counts(L, dA, n), _counts(L, dB, n))
+        assert same_records(rA, rB, layout) and torch.equal(gA, gB)
+        assert bank_cursor(L, dA) == bank_cursor(L, dB) and bank_cursor(L, dA) > 0
+        assert np.array_equal(reset_counts(L, dA, n), reset_counts(L, dB, n))
         assert folded >= 3, folded  # steps that took a pending reset
         assert rows_seen > 0
 
@@ -1242,7 +854,7 @@ def _graph_pair(n, B, F, seed0, bank_seed0, capture_reset):
     the reset_terminated inside the capture too), against an eager context A with
     the deferral off; both on the same scenes, bank and statistics."""
     caps = bench_caps(2)
-    P, layout, ctxs = _deferred_pair(n, B, F, caps, seed0, bank_seed0)
+    P, layout, ctxs = deferred_pair(n, B, F, caps, seed0, bank_seed0)
     L = lib()
     (dA, bankA, bfA, rA, gA, bA), (dB, bankB, bfB, rB, gB, bB) = ctxs
     check(L.cbev_set_deferred_reset(dA.ctx, 0), "deferred off")
@@ -1293,11 +905,11 @@ def _graph_pair(n, B, F, seed0, bank_seed0, capture_reset):
         torch.cuda.synchronize()
         for k in ("rew", "term", "trunc", "cause", "info"):
             assert torch.equal(bA[k], bB[k]), (rep, k)
-        assert _same_records(rA, rB, layout), (rep, "records")
+        assert same_records(rA, rB, layout), (rep, "records")
         assert torch.equal(gA, gB), (rep, "ring")
     check(L.cbev_flush(dB.ctx), "flush")
     torch.cuda.synchronize()
-    assert np.array_equal(_counts(L, dA, n), _counts(L, dB, n)) and _cursor(L, dA) > 0
+    assert np.array_equal(reset_counts(L, dA, n), reset_counts(L, dB, n)) and bank_cursor(L, dA) > 0
 
 
 def test_folded_step_under_graph_capture():
@@ -1341,7 +953,7 @@ def test_vector_env_reads_after_deferred_reset():
                 folded += lib().cbev_reset_pending(env._ctx)  # recorded, not launched
             outs.append((env._obs().clone(), env.records.clone(), env.term.clone()))
         assert torch.equal(outs[0][0], outs[1][0]), t
-        assert _same_records(outs[0][1], outs[1][1], envs[0].layout), t
+        assert same_records(outs[0][1], outs[1][1], envs[0].layout), t
         assert torch.equal(outs[0][2], outs[1][2]), t
         seen += int(outs[0][2].sum())
     assert seen > 0 and folded == 60
@@ -1356,7 +968,7 @@ def test_vector_env_reads_after_deferred_reset():
         env.reset_terminated()
         env.step(np.ones(24, np.int64))  # takes the reset
         env.step(np.zeros(24, np.int64))
-    assert _same_records(envs[0].records, envs[1].records, envs[0].layout)
+    assert same_records(envs[0].records, envs[1].records, envs[0].layout)
     assert torch.equal(envs[0].ring, envs[1].ring)
     assert torch.equal(envs[0].reward, envs[1].reward)
     for env in envs:

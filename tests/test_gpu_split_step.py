@@ -8,8 +8,6 @@ XCD-mapping boundary, actor capacities (8-env groups, actor scratch) and size
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -18,56 +16,14 @@ torch = pytest.importorskip("torch")
 import edge_cases as EC
 from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import check, lib
+from gpu_harness import (P_, DevWorld, assert_same, assert_same_outputs, flush_all, make_lanes, ptr, reset_counts,
+                         reset_terminated_all, step_all, term_of)
+from gpu_scenes import run_parity, split_pair
 from helpers import bench_caps, build_records, world
-from test_gpu_parity import DevWorld, EpisodeStatsOn, P_, _counts, _same_stats, ptr, run_parity
 
 pytestmark = pytest.mark.gpu
 
 CBEV_EINVAL = -1
-
-
-def _bufs(n):
-    return dict(rew=torch.zeros(n, dtype=torch.float64, device="cuda"),
-                term=torch.zeros(n, dtype=torch.uint8, device="cuda"),
-                trunc=torch.zeros(n, dtype=torch.uint8, device="cuda"),
-                cause=torch.zeros(n, dtype=torch.int32, device="cuda"),
-                info=torch.zeros((n, 16), dtype=torch.float32, device="cuda"))
-
-
-def _split_pair(n, caps, size, kinds, seed0, bank_seed0, n_bank=53, F=3, distinct=48, bank_distinct=17):
-    """Two contexts on the same records and bank, the unsplit step (0) and the
-    split step (1), the reset deferred into the next step and the episode
-    statistics on in both. The bank is test_stats_folded_reset_small's: every
-    third row starts off the road, so an env reset from it terminates in the step
-    that takes the reset; every second env starts off the road too, so the first
-    step already terminates some."""
-    cfg, P, padded, layout, builder = world(size, caps=caps)
-    base, _ = build_records(builder, min(n, distinct), list(kinds), seed0=seed0)
-    recs = base[np.arange(n) % len(base)].copy()
-    for e in range(0, n, 2):
-        LY.RecordView(recs[e], layout).hd[LY.HD["X"]] += 60.0
-    bdist, _ = build_records(builder, bank_distinct, list(kinds), seed0=bank_seed0)
-    bank = bdist[np.arange(n_bank) % bank_distinct].copy()
-    for b in range(0, n_bank, 3):
-        LY.RecordView(bank[b], layout).hd[LY.HD["X"]] += 60.0
-    L = lib()
-    S = P.size
-    out = []
-    for split in (0, 1):
-        dw = DevWorld(P, padded, caps)
-        check(L.cbev_set_split_step(dw.ctx, split), "split_step")
-        check(L.cbev_set_deferred_reset(dw.ctx, 1), "deferred")
-        d_bank = torch.from_numpy(bank.copy()).cuda()
-        bf = torch.zeros((n_bank, S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_bank_frames(dw.ctx, ptr(d_bank), n_bank, ptr(bf), None), "bank_frames")
-        d_recs = torch.from_numpy(recs.copy()).cuda()
-        ring = torch.zeros((F, n, S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), F, None), "reset")
-        b = _bufs(n)
-        b["stats"] = EpisodeStatsOn(dw.ctx, n)
-        out.append((dw, d_bank, bf, d_recs, ring, b))
-    return P, out
-
 
 CASES = [
     pytest.param(1, 2, 128, ("rt_no_traffic_v1",), id="n1"),
@@ -86,38 +42,25 @@ def test_split_equals_unsplit_bitwise(n, config, size, kinds):
     reset counts are equal after every step, and some env of the split context
     was reset and terminated in consecutive steps."""
     n_bank, F, steps = 53, 3, 40
-    P, ctxs = _split_pair(n, bench_caps(config), size, kinds, 10_300 + n, 14_300 + n, n_bank=n_bank, F=F)
+    P, lanes = split_pair(n, bench_caps(config), size, kinds, 10_300 + n, 14_300 + n, n_bank=n_bank, F=F)
     L = lib()
     rng = np.random.default_rng(n)
     p = np.ones(P.n_discrete)
     p[1] += 4.0
     acts = rng.choice(P.n_discrete, size=(steps, n), p=p / p.sum()).astype(np.int32)
-    (dA, _, _, rA, gA, bA), (dB, _, _, rB, gB, bB) = ctxs
+    A, B = lanes
     was_reset = np.zeros(n, bool)
     reset_then_term = 0
     for t in range(steps):
-        a = torch.from_numpy(np.ascontiguousarray(acts[t])).cuda()
-        for dw, d_bank, bf, d_recs, ring, b in ctxs:
-            check(L.cbev_step(dw.ctx, ptr(d_recs), n, ptr(a), ptr(ring[t % F]), ptr(b["rew"]), ptr(b["term"]),
-                              ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), None), "step")
-        torch.cuda.synchronize()
-        for k in ("rew", "term", "trunc", "cause", "info"):
-            assert torch.equal(bA[k], bB[k]), (t, k)
-        assert torch.equal(rA, rB), (t, "records")
-        assert torch.equal(gA, gB), (t, "ring")
-        assert _same_stats(bA["stats"], bB["stats"], t, n), (t, "episode stats")
-        assert np.array_equal(_counts(L, dA, n), _counts(L, dB, n)), (t, "reset counts")
-        tn = bB["term"].cpu().numpy().astype(bool)
+        step_all(lanes, acts[t], t)
+        assert_same(lanes, t)
+        tn = term_of(B)
         reset_then_term += int(np.sum(was_reset & tn))
         was_reset = tn
-        for dw, d_bank, bf, d_recs, ring, b in ctxs:
-            check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), n, ptr(d_bank), n_bank, ptr(bf), ptr(ring), F, None),
-                  "reset_terminated")
-    for dw, *_ in ctxs:
-        check(L.cbev_flush(dw.ctx), "flush")
-    torch.cuda.synchronize()
-    assert torch.equal(rA, rB) and torch.equal(gA, gB)
-    assert np.array_equal(_counts(L, dA, n), _counts(L, dB, n))
+        reset_terminated_all(lanes)
+    flush_all(lanes)
+    assert torch.equal(A.recs, B.recs) and torch.equal(A.ring, B.ring)
+    assert np.array_equal(reset_counts(L, A.dw, n), reset_counts(L, B.dw, n))
     assert reset_then_term > 0
 
 
@@ -159,17 +102,7 @@ def test_split_step_under_graph_capture():
     for e in range(0, n, 4):
         LY.RecordView(recs[e], layout).hd[LY.HD["X"]] += 60.0
     L = lib()
-    S = P.size
-    ctxs = []
-    for _ in range(2):
-        dw = DevWorld(P, padded, caps)
-        check(L.cbev_set_split_step(dw.ctx, 1), "split_step")
-        d_recs = torch.from_numpy(recs.copy()).cuda()
-        ring = torch.zeros((F, n, S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), F, None), "reset")
-        b = _bufs(n)
-        b["stats"] = EpisodeStatsOn(dw.ctx, n)
-        ctxs.append((dw, d_recs, ring, b))
+    lanes = make_lanes(P, padded, caps, recs, None, F, [dict(split=1)] * 2)
     acts = torch.ones(n, dtype=torch.int32, device="cuda")
 
     def step(dw, d_recs, ring, b):
@@ -177,10 +110,10 @@ def test_split_step_under_graph_capture():
                           ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]),
                           P_(torch.cuda.current_stream().cuda_stream)), "step")
 
-    for c in ctxs:  # one eager step each: the kernels are loaded before the capture
-        step(*c)
+    (dA, _, _, rA, gA, bA), (dB, _, _, rB, gB, bB) = lanes
+    step(dA, rA, gA, bA)  # one eager step each: the kernels are loaded before the capture
+    step(dB, rB, gB, bB)
     torch.cuda.synchronize()
-    (dA, rA, gA, bA), (dB, rB, gB, bB) = ctxs
     side = torch.cuda.Stream()
     g = torch.cuda.CUDAGraph()
     side.wait_stream(torch.cuda.current_stream())
@@ -193,9 +126,6 @@ def test_split_step_under_graph_capture():
         step(dA, rA, gA, bA)
         g.replay()
         torch.cuda.synchronize()
-        for k in ("rew", "term", "trunc", "cause", "info"):
-            assert torch.equal(bA[k], bB[k]), (rep, k)
-        assert torch.equal(rA, rB), (rep, "records")
-        assert torch.equal(gA, gB), (rep, "ring")
+        assert_same_outputs(*lanes, rep)
     assert int(bA["term"].sum()) > 0  # the envs pushed off the road terminate in every step
     assert L.cbev_reset_pending(dB.ctx) == 0

@@ -7,7 +7,6 @@ run the same arithmetic, there is no tolerance to choose.
 """
 from __future__ import annotations
 
-import ctypes
 from collections import deque
 
 import numpy as np
@@ -18,12 +17,11 @@ torch = pytest.importorskip("torch")
 from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import check, lib
 from carlabev_env_amd.semantics import gray_lut, semantic_lut, semantic_mask_channels
+from gpu_harness import (KEYS, P_, DevWorld, EpisodeStatsOn, assert_same_outputs, error_flags, out_bufs, ptr,
+                         reset_counts, same_stats, step_masked, termination_count)
+from gpu_scenes import (CODES, EGO_ONLY, GUARD, cout, dtypes_of, ego_only_64, eval_actions, eval_cfg, eval_pair,
+                        mask_stream, obs_world, out_bytes, relaid, twins)
 from helpers import CAPS_FULL, action_stream, bench_caps, build_records, world
-from test_gpu_masked_step import (EGO_ONLY, KEYS, _eval_actions, _eval_cfg, _eval_pair, _nterm, _twins, ego_only_64,
-                                  mask_stream, step_masked)
-from test_gpu_obs_dtype import CODES, GUARD, Ctx, cout, dtypes_of, out_bytes
-from test_gpu_parity import DevWorld, EpisodeStatsOn, P_, _counts, _same_stats, error_flags, ptr
-from test_gpu_split_step import _bufs
 
 pytestmark = pytest.mark.gpu
 
@@ -34,15 +32,6 @@ MODE = "7-class"  # a semantic mode with a vehicle channel: the three fusions ap
 def step_heads(L, dw, d_recs, n, a, act, k, ring, F, heads, b, stream=None):
     return L.cbev_step_heads(dw.ctx, ptr(d_recs), n, ptr(a), ptr(act), k, ptr(ring), F, ptr(heads), ptr(b["rew"]),
                              ptr(b["term"]), ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), stream)
-
-
-def relaid(ring: torch.Tensor, heads: torch.Tensor) -> torch.Tensor:
-    """ring2[f][e] = ring[(heads[e] + 1 + f) % F][e]: the ring whose global head F - 1 shows
-    every env's frames in its own head order (oldest first)."""
-    F, n = ring.shape[:2]
-    f = torch.arange(F, device=ring.device)[:, None]
-    slot = (heads.long()[None, :] + 1 + f) % F
-    return ring[slot, torch.arange(n, device=ring.device)[None, :]].contiguous()
 
 
 # ---------------------------------------------------------------------- 1. the expansion
@@ -82,7 +71,7 @@ EXPAND_CASES = [
 
 @pytest.mark.parametrize("hw,n,F,off_elems", EXPAND_CASES)
 def test_expansion_equals_the_global_head_kernels_on_the_relaid_ring(hw, n, F, off_elems):
-    c = Ctx(hw)
+    c = obs_world(hw)
     P = hw[0] * hw[1]
     rng = np.random.default_rng(1000 * hw[0] + 10 * F + off_elems)
     ring = torch.from_numpy(rng.integers(0, 10, (F, n, *hw)).astype(np.uint8)).cuda()
@@ -105,7 +94,7 @@ def test_expansion_equals_the_global_head_kernels_on_the_relaid_ring(hw, n, F, o
 
 def test_a_head_byte_out_of_range_stays_inside_the_ring():
     hw, n, F = (64, 64), 13, 4
-    c = Ctx(hw)
+    c = obs_world(hw)
     rng = np.random.default_rng(5)
     ring = torch.from_numpy(rng.integers(0, 10, (F, n, *hw)).astype(np.uint8)).cuda()
     h = (np.arange(n) % F).astype(np.uint8)
@@ -127,7 +116,7 @@ def test_a_head_byte_out_of_range_stays_inside_the_ring():
 
 
 def test_expansion_refusals():
-    c = Ctx((64, 64))
+    c = obs_world((64, 64))
     L = lib()
     buf = torch.zeros(4 * 64 * 64 * 64, dtype=torch.uint8, device="cuda")
     ring, heads = buf[:3 * 64 * 64], buf[:1]
@@ -207,7 +196,7 @@ def test_step_heads_equals_step_masked_on_one_slot(case):
         d_recs = torch.from_numpy(recs.copy()).cuda()
         ring = torch.zeros((nf, n, S, S), dtype=torch.uint8, device="cuda")
         check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), nf, None), "reset")
-        b = _bufs(n)
+        b = out_bufs(n)
         b["stats"] = EpisodeStatsOn(dw.ctx, n)
         twins.append((dw, d_recs, ring, b))
     (dA, rA, fA, bA), (dB, rB, gB, bB) = twins
@@ -231,10 +220,10 @@ def test_step_heads_equals_step_masked_on_one_slot(case):
         assert torch.equal(rA, rB), (t, "records")
         for key in KEYS:
             assert torch.equal(bA[key], bB[key]), (t, key)
-        assert _same_stats(bA["stats"], bB["stats"], t, n), (t, "episode stats")
+        assert same_stats(bA["stats"], bB["stats"], t, n), (t, "episode stats")
         assert torch.equal(bA["stats"].counts, bB["stats"].counts), (t, "row counts")
-        assert np.array_equal(_counts(L, dA, n), _counts(L, dB, n)), (t, "reset counts")
-        assert _nterm(L, dA) == _nterm(L, dB), (t, "termination count")
+        assert np.array_equal(reset_counts(L, dA, n), reset_counts(L, dB, n)), (t, "reset counts")
+        assert termination_count(L, dA) == termination_count(L, dB), (t, "termination count")
         h[act] = (h[act] + 1) % F  # once per call, whatever k is
         assert np.array_equal(heads.cpu().numpy(), h), (t, "heads")
         assert torch.equal(gB[heads.long(), ar], fA[0]), (t, "the newest frame")
@@ -259,7 +248,7 @@ def test_step_heads_equals_step_masked_on_one_slot(case):
 def _pair(monkeypatch, N, max_actions=200, obs_mode="bev_semantic", **kw):
     """A default env and a stack_heads="per_env" one on the same seeded reset."""
     from carlabev_env_amd import RandomNavigationReset, build_random_navigation_options, make_env
-    cfg = _eval_cfg(monkeypatch, max_actions).model_copy(update={"obs_mode": obs_mode})
+    cfg = eval_cfg(monkeypatch, max_actions).model_copy(update={"obs_mode": obs_mode})
     envs = [make_env({"env": cfg, "num_envs": N}, num_envs=N, caps=EGO_ONLY, stack_heads=sh, **kw)
             for sh in ("global", "per_env")]
     opts = build_random_navigation_options(RandomNavigationReset(difficulty_id="rt_no_traffic_v1"))
@@ -279,7 +268,7 @@ def test_time_warp_invariance(monkeypatch, obs_mode, obs_dtype):
     (plain, warped), _ = _pair(monkeypatch, N, obs_mode=obs_mode, obs_dtype=obs_dtype)
     assert warped.stack_heads == "per_env" and warped.F == 4 and warped.heads.dtype == torch.uint8
     assert plain.stack_heads == "global" and plain.heads is None
-    a = np.stack([_eval_actions(N, t) for t in range(T)]).astype(np.int32)
+    a = np.stack([eval_actions(N, t) for t in range(T)]).astype(np.int32)
     obs_A, term_A = [], []
     for t in range(T):
         o, _, term, _, _ = plain.step(a[t])
@@ -320,7 +309,7 @@ def test_plain_steps_in_per_env_mode_equal_the_default_env(monkeypatch):
     N = 24
     (plain, heads), _ = _pair(monkeypatch, N, action_repeat=2)
     for t in range(6):
-        a = _eval_actions(N, t)
+        a = eval_actions(N, t)
         x, y = plain.step(a), heads.step(a)
         assert all(torch.equal(p, q) for p, q in zip(x[:4], y[:4])), t
     assert torch.equal(heads.heads, torch.full((N,), 6 % 4, dtype=torch.uint8, device="cuda"))
@@ -332,7 +321,7 @@ def test_freeze_done_with_per_env_heads(monkeypatch):
     """One episode per env, and a finished env's observation stays bit-identical
     from its terminal step until all_done()."""
     N, max_actions = 24, 40
-    envs, _ = _eval_pair(monkeypatch, N, max_actions, stack_heads="per_env")
+    envs, _ = eval_pair(monkeypatch, N, max_actions, stack_heads="per_env")
     frozen, plain = envs
     assert frozen.freeze_done and frozen.stack_heads == "per_env" and plain.stack_heads == "per_env"
     got, first = {}, {}
@@ -340,7 +329,7 @@ def test_freeze_done_with_per_env_heads(monkeypatch):
     kept, steps, prev = 0, 0, None
     while not frozen.all_done():
         assert steps < max_actions + 2, "the evaluation did not end"
-        a = _eval_actions(N, steps)
+        a = eval_actions(N, steps)
         o, r, term, _, infos = frozen.step(a)
         _, _, _, _, infos1 = plain.step(a)
         for e in np.flatnonzero(done):
@@ -370,7 +359,7 @@ def test_resets_in_per_env_mode_equal_the_default_env(monkeypatch):
     (plain, heads), opts = _pair(monkeypatch, N)
     rng = np.random.default_rng(8)
     for t in range(5):
-        a = _eval_actions(N, t)
+        a = eval_actions(N, t)
         plain.step(a)
         heads.step(a, active=torch.from_numpy(rng.random(N) < 0.5).cuda())
     assert len(set(heads.heads.cpu().numpy().tolist())) > 1
@@ -397,7 +386,7 @@ def test_step_and_expansion_under_graph_capture():
     with the mask edited in place in between equal two eager pairs on a twin: the
     heads are advanced on the device, so a replay continues where the last stopped."""
     n, F, k = 19, 3, 2
-    P, ctxs = _twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_719, 14_719, F=F)
+    P, lanes = twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_719, 14_719, F=F)
     L = lib()
     S = P.size
     C = len(semantic_mask_channels(MODE))
@@ -408,7 +397,7 @@ def test_step_and_expansion_under_graph_capture():
     assert not torch.equal(masks[1], masks[2])
     m_graph = masks[0].clone()
     state = [dict(heads=torch.zeros(n, dtype=torch.uint8, device="cuda"),
-                  obs=torch.zeros((n, F * C, S, S), dtype=torch.float32, device="cuda")) for _ in ctxs]
+                  obs=torch.zeros((n, F * C, S, S), dtype=torch.float32, device="cuda")) for _ in lanes]
 
     def step(c, st, m):
         dw, _, _, d_recs, ring, b = c
@@ -417,7 +406,7 @@ def test_step_and_expansion_under_graph_capture():
         check(L.cbev_expand_obs_heads(dw.ctx, ptr(ring), n, F, ptr(st["heads"]), 0, C, lut.ctypes.data_as(P_),
                                       CODES["float32"], ptr(st["obs"]), s), "expand_heads")
 
-    A, B = ctxs
+    A, B = lanes
     step(A, state[0], masks[0])  # one eager pair each: the kernels are loaded before the capture
     step(B, state[1], m_graph)
     torch.cuda.synchronize()
@@ -428,29 +417,26 @@ def test_step_and_expansion_under_graph_capture():
         with torch.cuda.graph(g, stream=side):
             step(B, state[1], m_graph)
     torch.cuda.synchronize()
-    assert torch.equal(A[3], B[3]) and torch.equal(state[0]["heads"], state[1]["heads"])  # the capture ran nothing
+    assert torch.equal(A.recs, B.recs) and torch.equal(state[0]["heads"], state[1]["heads"])  # the capture ran nothing
     for rep in (1, 2):
         step(A, state[0], masks[rep])
         m_graph.copy_(masks[rep])
         g.replay()
         torch.cuda.synchronize()
-        for key in KEYS:
-            assert torch.equal(A[5][key], B[5][key]), (rep, key)
-        assert torch.equal(A[3], B[3]), (rep, "records")
-        assert torch.equal(A[4], B[4]), (rep, "ring")
+        assert_same_outputs(A, B, rep)
         assert torch.equal(state[0]["heads"], state[1]["heads"]), (rep, "heads")
         assert torch.equal(state[0]["obs"], state[1]["obs"]), (rep, "observation")
     want = sum(m.long() for m in masks) % F
     assert torch.equal(state[1]["heads"].long(), want)
-    assert int(A[5]["term"].sum()) > 0
+    assert int(A.out["term"].sum()) > 0
 
 
 # ---------------------------------------------------------------------- 7. refusals
 def test_refusals_leave_a_live_context_untouched():
     n, F = 19, 3
-    P, ctxs = _twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_819, 14_819, F=F)
+    P, lanes = twins(n, bench_caps(2), 128, ("rt_no_traffic_v1",), 10_819, 14_819, F=F)
     L = lib()
-    dw, d_bank, bf, d_recs, _, b = ctxs[0]
+    dw, d_bank, bf, d_recs, _, b = lanes[0]
     S = P.size
     store = torch.zeros(F * n * S * S + 16, dtype=torch.uint8, device="cuda")
     ring = store[:F * n * S * S].view(F, n, S, S)
@@ -464,7 +450,7 @@ def test_refusals_leave_a_live_context_untouched():
     st = b["stats"]
     before = [d_recs.clone(), store.clone(), heads.clone(), st.stats.clone(), st.rows.clone(), st.counts.clone()] + [
         b[key].clone() for key in KEYS]
-    counts0, nterm0 = _counts(L, dw, n), _nterm(L, dw)
+    counts0, nterm0 = reset_counts(L, dw, n), termination_count(L, dw)
 
     def call(act=ones, ring_=ring, heads_=heads, k=2, n_=n, nf=F):
         return L.cbev_step_heads(dw.ctx, ptr(d_recs), n_, ptr(acts), ptr(act), k, ptr(ring_), nf, ptr(heads_),
@@ -482,7 +468,7 @@ def test_refusals_leave_a_live_context_untouched():
     torch.cuda.synchronize()
     after = [d_recs, store, heads, st.stats, st.rows, st.counts] + [b[key] for key in KEYS]
     assert all(torch.equal(x, y) for x, y in zip(before, after))
-    assert np.array_equal(_counts(L, dw, n), counts0) and _nterm(L, dw) == nterm0
+    assert np.array_equal(reset_counts(L, dw, n), counts0) and termination_count(L, dw) == nterm0
     assert error_flags(dw.ctx) == 0
     check(step_heads(L, dw, d_recs, n, good, ones, 64, ring, F, heads, b), "step_heads")  # the largest repeat runs
     torch.cuda.synchronize()

@@ -17,9 +17,8 @@ torch = pytest.importorskip("torch")
 
 from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import REPEAT_MAX, check, lib
+from gpu_harness import KEYS, error_flags, make_lane, ptr
 from helpers import action_stream, build_records, world
-from test_gpu_parity import DevWorld, EpisodeStatsOn, error_flags, ptr
-from test_gpu_split_step import _bufs
 
 pytestmark = pytest.mark.gpu
 
@@ -28,7 +27,6 @@ N, F, B, SIZE = 8, 3, 5, 128
 CAPS = {"ego": (LY.Caps(64, 0, 2, 0), ("rt_no_traffic_v1",)),  # no actors kernel, a reset can be deferred
         "actors": (LY.Caps(64, 4, 288, 4), ("mix3",))}          # the actors launches run
 ENTRIES = ("step", "repeat", "masked", "heads")
-KEYS = ("rew", "term", "trunc", "cause", "info")
 _HOST = {}
 
 
@@ -54,24 +52,14 @@ class World:
     cbev_step_heads."""
 
     def __init__(self, kind, deferred=0, profile=True):
-        L = lib()
         self.P, padded, caps, recs, bank = _host(kind)
-        self.dw = DevWorld(self.P, padded, caps)
-        self.ctx = self.dw.ctx
-        check(L.cbev_set_split_step(self.ctx, 0), "split off")
-        check(L.cbev_set_deferred_reset(self.ctx, deferred), "deferred")
-        self.bank = torch.from_numpy(bank.copy()).cuda()
-        self.bank_frames = torch.zeros((B, SIZE, SIZE), dtype=torch.uint8, device="cuda")
-        check(L.cbev_bank_frames(self.ctx, ptr(self.bank), B, ptr(self.bank_frames), None), "bank_frames")
-        self.recs = torch.from_numpy(recs.copy()).cuda()
-        self.ring = torch.zeros((F, N, SIZE, SIZE), dtype=torch.uint8, device="cuda")
-        check(L.cbev_reset(self.ctx, ptr(self.recs), N, None, 0, None, None, 0, ptr(self.ring), F, None), "reset")
+        lane = make_lane(self.P, padded, caps, recs, bank, F, split=0, deferred=deferred)
+        self.dw, self.bank, self.bank_frames, self.recs, self.ring, self.b = lane
+        self.ctx, self.stats = self.dw.ctx, self.b["stats"]
         self.heads = torch.from_numpy((np.arange(N) % F).astype(np.uint8)).cuda()
         self.ones = torch.ones(N, dtype=torch.uint8, device="cuda")
-        self.b = _bufs(N)
-        self.stats = EpisodeStatsOn(self.ctx, N)
         if profile:
-            check(L.cbev_profile(self.ctx, 1), "profile")
+            check(lib().cbev_profile(self.ctx, 1), "profile")
         self.slot = 0  # the ring slot of the newest frame (step, repeat, masked)
 
     def call(self, entry, a, repeat=1, n=N, rew="rew", frames=None, n_frames=F):

@@ -17,105 +17,16 @@ torch = pytest.importorskip("torch")
 
 import edge_cases as EC
 from carlabev_env_amd import layout as LY
-from carlabev_env_amd._lib import check, lib
+from carlabev_env_amd._lib import lib
+from gpu_harness import (assert_same, error_flags, flush_all, reset_counts, reset_rows, reset_terminated_all, step_all,
+                         term_of)
+from gpu_scenes import CAPS_LONG2, CAPS_LONG3, N_BANK, long_records, run_parity, split_lanes
 from helpers import bench_caps
-from test_gpu_parity import DevWorld, EpisodeStatsOn, _counts, _same_stats, error_flags, ptr, reset_rows, run_parity
-from test_gpu_split_step import _bufs
 
 pytestmark = pytest.mark.gpu
 
 CB_DT = 0.1
 WHEELBASE = 2.9
-N_BANK, F = 53, 3
-# the bench's capacities of configs 2 (ego only: the reset folds into the step)
-# and 3 (25 actor slots: 8 envs per tail group) with room for 128-point routes
-CAPS_LONG2 = LY.Caps(128, 0, 2, 0)
-CAPS_LONG3 = LY.Caps(128, 25, 288, 0)
-
-
-def _off_road_dy(x, y):
-    """A row offset that takes (x, y) off the drivable texels of the 128 map."""
-    _, _, classes = EC.authored_world(128)
-    for d in range(8, 200):
-        for dy in (d, -d):
-            if 0 <= int(y) + dy < classes.shape[0] and classes[int(y) + dy, int(x)] != 1:
-                return float(dy)
-    raise AssertionError("no off-road texel above or below the road")
-
-
-def _long_records(n, caps, seed0, off_every):
-    """n records with ego routes of 65, 127, 128, 64 and 33 points (long_route_spec),
-    each placed on a route point and driving at 30 px/s; every off_every-th one
-    starts off the road, so it terminates in its first step."""
-    lengths = (65, 127, 128, 64, 33)
-    specs = []
-    for e in range(n):
-        s = EC.long_route_spec(lengths[e % len(lengths)], 128, seed=seed0 + e)
-        if caps.actor_cap == 0:
-            s = dataclasses.replace(s, vehicles=[], pedestrians=[])
-        specs.append(s)
-    recs, layout, views = EC.pack_records(specs, 128, caps)
-    for e, v in enumerate(views):
-        nr = v.i("NROUTE")
-        i = (7 * e + 3) % (nr - 1)
-        EC.set_pose(v, v.cx[i], v.cy[i], v.cyaw[i], 30.0)
-        if e % 2 == 0:
-            v.hi[LY.HI["TIDX"]] = i
-        if e % off_every == 0:
-            v.hd[LY.HD["Y"]] += _off_road_dy(v.cx[i], v.cy[i])
-    return recs, layout
-
-
-def _pair(P, padded, caps, recs, bank):
-    """The unsplit step (0) and the split step (1) on the same records and bank,
-    the reset deferred into the next step, a 3-slot ring, the statistics on."""
-    L = lib()
-    S, n = P.size, len(recs)
-    out = []
-    for split in (0, 1):
-        dw = DevWorld(P, padded, caps)
-        check(L.cbev_set_split_step(dw.ctx, split), "split_step")
-        check(L.cbev_set_deferred_reset(dw.ctx, 1), "deferred")
-        d_bank = torch.from_numpy(bank.copy()).cuda()
-        bf = torch.zeros((len(bank), S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_bank_frames(dw.ctx, ptr(d_bank), len(bank), ptr(bf), None), "bank_frames")
-        d_recs = torch.from_numpy(recs.copy()).cuda()
-        ring = torch.zeros((F, n, S, S), dtype=torch.uint8, device="cuda")
-        check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), F, None), "reset")
-        b = _bufs(n)
-        b["stats"] = EpisodeStatsOn(dw.ctx, n)
-        out.append((dw, d_bank, bf, d_recs, ring, b))
-    return out
-
-
-def _step(ctxs, acts_t, t):
-    L = lib()
-    a = torch.from_numpy(np.ascontiguousarray(acts_t)).cuda()
-    for dw, d_bank, bf, d_recs, ring, b in ctxs:
-        check(L.cbev_step(dw.ctx, ptr(d_recs), len(d_recs), ptr(a), ptr(ring[t % F]), ptr(b["rew"]), ptr(b["term"]),
-                          ptr(b["trunc"]), ptr(b["cause"]), ptr(b["info"]), None), "step")
-    torch.cuda.synchronize()
-
-
-def _reset_terminated(ctxs):
-    L = lib()
-    for dw, d_bank, bf, d_recs, ring, b in ctxs:
-        check(L.cbev_reset_terminated(dw.ctx, ptr(d_recs), len(d_recs), ptr(d_bank), len(d_bank), ptr(bf), ptr(ring),
-                                      F, None), "reset_terminated")
-
-
-def _assert_same(ctxs, t):
-    """Records, the ring, reward, term, trunc, cause, info, episode rows and counts,
-    reset counts: the split context's equal the unsplit one's, bitwise."""
-    L = lib()
-    (dA, _, _, rA, gA, bA), (dB, _, _, rB, gB, bB) = ctxs
-    n = len(rA)
-    for k in ("rew", "term", "trunc", "cause", "info"):
-        assert torch.equal(bA[k], bB[k]), (t, k)
-    assert torch.equal(rA, rB), (t, "records", torch.nonzero((rA != rB).any(1)).flatten()[:8].tolist())
-    assert torch.equal(gA, gB), (t, "ring")
-    assert _same_stats(bA["stats"], bB["stats"], t, n), (t, "episode stats")
-    assert np.array_equal(_counts(L, dA, n), _counts(L, dB, n)), (t, "reset counts")
 
 
 @pytest.mark.parametrize("caps", [CAPS_LONG2, CAPS_LONG3], ids=["ego-only", "config3-actors"])
@@ -126,10 +37,10 @@ def test_split_equals_unsplit_bitwise_long_routes(caps):
     some env, and some env was reset and terminated in consecutive steps."""
     n, steps = 19, 40
     P, padded, _ = EC.authored_world(128)
-    recs, layout = _long_records(n, caps, 100, off_every=2)
-    bank, _ = _long_records(N_BANK, caps, 500, off_every=3)
+    recs, layout = long_records(n, caps, 100, off_every=2)
+    bank, _ = long_records(N_BANK, caps, 500, off_every=3)
     assert max(LY.RecordView(r, layout).i("NROUTE") for r in recs) > 64
-    ctxs = _pair(P, padded, caps, recs, bank)
+    lanes = split_lanes(P, padded, caps, recs, bank)
     rng = np.random.default_rng(19)
     p = np.ones(P.n_discrete)
     p[1] += 4.0
@@ -137,18 +48,16 @@ def test_split_equals_unsplit_bitwise_long_routes(caps):
     was_reset = np.zeros(n, bool)
     reset_then_term, tidx_max = 0, 0
     for t in range(steps):
-        _step(ctxs, acts[t], t)
-        _assert_same(ctxs, t)
-        tn = ctxs[1][5]["term"].cpu().numpy().astype(bool)
+        step_all(lanes, acts[t], t)
+        assert_same(lanes, t)
+        tn = term_of(lanes[1])
         reset_then_term += int(np.sum(was_reset & tn))
         was_reset = tn
-        hr = ctxs[1][3].cpu().numpy()
+        hr = lanes[1].recs.cpu().numpy()
         tidx_max = max(tidx_max, max(LY.RecordView(hr[e], layout).i("TIDX") for e in range(n)))
-        _reset_terminated(ctxs)
-    for dw, *_ in ctxs:
-        check(lib().cbev_flush(dw.ctx), "flush")
-    torch.cuda.synchronize()
-    assert torch.equal(ctxs[0][3], ctxs[1][3]) and torch.equal(ctxs[0][4], ctxs[1][4])
+        reset_terminated_all(lanes)
+    flush_all(lanes)
+    assert torch.equal(lanes[0].recs, lanes[1].recs) and torch.equal(lanes[0].ring, lanes[1].ring)
     assert reset_then_term > 0 and tidx_max > 64
 
 
@@ -179,33 +88,33 @@ def test_reset_composition_of_a_head_group(head_ne, edit_after, monkeypatch):
         if b % 2 == 0:  # a row saved mid-episode: comfort history present
             v.hi[LY.HI["HAS_PREV_COMFORT"]] = 1
             v.hd[LY.HD["PREV_AL"]], v.hd[LY.HD["PREV_ALAT"]], v.hd[LY.HD["PREV_YR"]] = 0.75, -0.25, 2.0
-    ctxs = _pair(P, padded, caps, recs, bank)
+    lanes = split_lanes(P, padded, caps, recs, bank)
     acts = np.ones((2, n), np.int32)
-    _step(ctxs, acts[0], 0)
-    _assert_same(ctxs, 0)
+    step_all(lanes, acts[0], 0)
+    assert_same(lanes, 0)
     mask = np.zeros(n, np.uint8)
     mask[0:head_ne] = 1                                    # every env of group 0
     mask[2 * head_ne:3 * head_ne:3] = 1                    # a mix in group 2 (group 1: none)
     mask[2 * head_ne + 1] = 1
     mask[3 * head_ne + 1] = 1                              # one of the partial last group
     L = lib()
-    tcount = _counts(L, ctxs[1][0], n)
+    tcount = reset_counts(L, lanes[1].dw, n)
     m = torch.from_numpy(mask).cuda()
     if not edit_after:
-        for c in ctxs:
-            c[5]["term"].copy_(m)
-    _reset_terminated(ctxs)
+        for c in lanes:
+            c.out["term"].copy_(m)
+    reset_terminated_all(lanes)
     if edit_after:
-        for c in ctxs:
-            c[5]["term"].copy_(m)
+        for c in lanes:
+            c.out["term"].copy_(m)
     torch.cuda.synchronize()
-    _step(ctxs, acts[1], 1)
-    _assert_same(ctxs, 1)
+    step_all(lanes, acts[1], 1)
+    assert_same(lanes, 1)
     ids, rows = reset_rows(mask, tcount, N_BANK)
     h = head_ne
     assert mask[:h].all() and not mask[h:2 * h].any() and 0 < mask[2 * h:3 * h].sum() < h and mask[3 * h:].sum() == 1
     assert len(ids) == int(mask.sum())
-    hr = ctxs[1][3].cpu().numpy()
+    hr = lanes[1].recs.cpu().numpy()
     seen_prev = set()
     for e, row in zip(ids, rows):
         v, bv = LY.RecordView(hr[e], layout), LY.RecordView(bank[row], layout)
@@ -219,7 +128,7 @@ def test_reset_composition_of_a_head_group(head_ne, edit_after, monkeypatch):
             assert v.h(out) == want, (e, out, v.h(out), want)
     assert seen_prev == {0, 1}
     kept = np.flatnonzero(mask == 0)
-    h0 = ctxs[0][3].cpu().numpy()
+    h0 = lanes[0].recs.cpu().numpy()
     assert all(LY.RecordView(h0[e], layout).i("SCENE_ID") == e for e in kept)
 
 
@@ -265,18 +174,18 @@ def test_target_search_ties_take_the_first_argmin(caps):
         assert np.count_nonzero(d == d[bi]) == 2 and bi < 50  # a tie, and its first index
         want.append(max(v.i("TIDX"), bi))
     acts = np.ones((steps, n), np.int32)
-    ctxs = _pair(P, padded, caps, recs, recs[np.arange(N_BANK) % n].copy())
+    lanes = split_lanes(P, padded, caps, recs, recs[np.arange(N_BANK) % n].copy())
     prev = np.array([LY.RecordView(recs[e], layout).i("TIDX") for e in range(n)])
     for t in range(steps):
-        _step(ctxs, acts[t], t)
-        _assert_same(ctxs, t)
-        hr = ctxs[1][3].cpu().numpy()
+        step_all(lanes, acts[t], t)
+        assert_same(lanes, t)
+        hr = lanes[1].recs.cpu().numpy()
         tidx = np.array([LY.RecordView(hr[e], layout).i("TIDX") for e in range(n)])
         if t == 0:
             assert tidx.tolist() == want, (tidx, want)
         assert np.all(tidx >= prev) and tidx[2] == 80
         prev = tidx
-    del ctxs
+    del lanes
     run_parity(None, n, steps, caps=caps, recs=recs, world_=(P, padded), acts=acts, stats=True)
 
 
@@ -296,32 +205,32 @@ def test_action_index_out_of_range_in_reset_and_kept_envs():
     caps = CAPS_LONG2
     n = 19
     P, padded, _ = EC.authored_world(128)
-    recs, layout = _long_records(n, caps, 900, off_every=1000)
-    bank, _ = _long_records(N_BANK, caps, 950, off_every=1000)
-    ctxs = _pair(P, padded, caps, recs, bank)
+    recs, layout = long_records(n, caps, 900, off_every=1000)
+    bank, _ = long_records(N_BANK, caps, 950, off_every=1000)
+    lanes = split_lanes(P, padded, caps, recs, bank)
     acts = np.ones((2, n), np.int32)
-    _step(ctxs, acts[0], 0)
-    _assert_same(ctxs, 0)
-    assert error_flags(ctxs[0][0].ctx) == 0 and error_flags(ctxs[1][0].ctx) == 0
+    step_all(lanes, acts[0], 0)
+    assert_same(lanes, 0)
+    assert error_flags(lanes[0].dw.ctx) == 0 and error_flags(lanes[1].dw.ctx) == 0
     mask = np.zeros(n, np.uint8)
     mask[[2, 17]] = 1
-    for c in ctxs:
-        c[5]["term"].copy_(torch.from_numpy(mask).cuda())
-    _reset_terminated(ctxs)
+    for c in lanes:
+        c.out["term"].copy_(torch.from_numpy(mask).cuda())
+    reset_terminated_all(lanes)
     acts[1, 2] = P.n_discrete + 5   # in a reset env
     acts[1, 7] = -P.n_discrete - 1  # in a kept env
-    _step(ctxs, acts[1], 1)
-    _assert_same(ctxs, 1)
-    fa, fb = error_flags(ctxs[0][0].ctx), error_flags(ctxs[1][0].ctx)
+    step_all(lanes, acts[1], 1)
+    assert_same(lanes, 1)
+    fa, fb = error_flags(lanes[0].dw.ctx), error_flags(lanes[1].dw.ctx)
     assert fa == fb and fa != 0
     # stepped as action 0 in both envs
     ref = acts[1].copy()
     ref[[2, 7]] = 0
-    ctxs2 = _pair(P, padded, caps, recs, bank)
-    _step(ctxs2, acts[0], 0)
-    for c in ctxs2:
-        c[5]["term"].copy_(torch.from_numpy(mask).cuda())
-    _reset_terminated(ctxs2)
-    _step(ctxs2, ref, 1)
-    assert torch.equal(ctxs2[1][3], ctxs[1][3]) and torch.equal(ctxs2[1][5]["rew"], ctxs[1][5]["rew"])
-    assert error_flags(ctxs2[1][0].ctx) == 0
+    lanes2 = split_lanes(P, padded, caps, recs, bank)
+    step_all(lanes2, acts[0], 0)
+    for c in lanes2:
+        c.out["term"].copy_(torch.from_numpy(mask).cuda())
+    reset_terminated_all(lanes2)
+    step_all(lanes2, ref, 1)
+    assert torch.equal(lanes2[1].recs, lanes[1].recs) and torch.equal(lanes2[1].out["rew"], lanes[1].out["rew"])
+    assert error_flags(lanes2[1].dw.ctx) == 0

@@ -9,8 +9,6 @@ matches exact colours; grayscale is the same float64 dot product, truncated.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -19,29 +17,13 @@ torch = pytest.importorskip("torch")
 import wrappers as W
 from carlabev_env_amd._lib import check, lib
 from carlabev_env_amd.semantics import gray_lut, semantic_lut, semantic_mask_channels
-from helpers import CAPS_FULL, world
+from gpu_harness import P_, ptr
+from gpu_scenes import obs_world
 
 pytestmark = pytest.mark.gpu
 
-P_ = ctypes.c_void_p
 MODES = ("binary", "2-class", "4-class", "5-class", "6-class", "7-class")
 VMODES = ("4-class", "5-class", "6-class", "7-class")
-
-
-def ptr(t):
-    return P_(t.data_ptr()) if t is not None else None
-
-
-class Ctx:
-    def __init__(self, size=128):
-        cfg, P, padded, layout, builder = world(size=size)
-        self.P = P
-        self.ctx = P_()
-        check(lib().cbev_create(ctypes.byref(P), ctypes.byref(CAPS_FULL.c()), 0, ctypes.byref(self.ctx)), "create")
-        check(lib().cbev_set_map(self.ctx, padded.ctypes.data_as(P_), padded.nbytes), "set_map")
-
-    def __del__(self):
-        lib().cbev_destroy(self.ctx)
 
 
 def blocky_ids(rng, n, S, k=8):
@@ -63,7 +45,7 @@ def expand(c, ring_d, n, F, head, kind, C, lut, out):
 
 @pytest.mark.parametrize("F,head", [(4, 1), (3, 0), (5, 4)])
 def test_expand_semantic_stack_and_fusions(F, head):
-    c = Ctx()
+    c = obs_world()
     S, n = 128, 9
     rng = np.random.default_rng(F * 10 + head)
     ring_h = rng.integers(0, 10, (F, n, S, S)).astype(np.uint8)
@@ -85,7 +67,7 @@ def test_expand_semantic_stack_and_fusions(F, head):
 
 
 def test_expand_rejects_fusion_without_vehicle_channel():
-    c = Ctx()
+    c = obs_world()
     ring = torch.zeros((4, 2, 128, 128), dtype=torch.uint8, device="cuda")
     out = torch.zeros((2, 4, 128, 128), dtype=torch.float32, device="cuda")
     for mode in ("binary", "2-class"):
@@ -98,7 +80,7 @@ def test_expand_rejects_fusion_without_vehicle_channel():
 
 @pytest.mark.parametrize("hw", [(96, 96), (64, 64), (84, 84), (96, 80), (100, 128), (32, 32)])
 def test_resize_matches_inter_area_oracle(hw):
-    c = Ctx()
+    c = obs_world()
     S, n = 128, 6
     rng = np.random.default_rng(hw[0] * 1000 + hw[1])
     ids = blocky_ids(rng, n, S)
@@ -136,7 +118,7 @@ def test_resize_matches_inter_area_oracle(hw):
 
 
 def test_resize_rejects_upscale():
-    c = Ctx()
+    c = obs_world()
     assert lib().cbev_set_obs_size(c.ctx, 160, 128) != 0
 
 
