@@ -506,3 +506,368 @@ def retreat_raw_route(view, slot, cur):
     px = [view.ad[LY.AD["X"], slot]] + list(view.aix[slot, :cur + 1][::-1])
     py = [view.ad[LY.AD["Y"], slot]] + list(view.aiy[slot, :cur + 1][::-1])
     return np.array(px), np.array(py)
+
+
+# ------------------------------------------------------------------ the actor target search
+# calc_target_index of a scripted actor (stanley_controller.py:100-123): the
+# kernel's actor_search / actor_search_win<AW> against
+#     max(tid0, int(np.argmin(np.hypot(cx - fx, cy - fy))))
+# in float64 NumPy (expected_tidx). Every searching actor stands still (speed 0)
+# at yaw exactly 0, so a second step repeats the search from the index the
+# first one chose. Its front axle is fx = x + 2.9 * cos(0) = fl(x + 2.9), fy =
+# y + 2.9 * sin(0) = y: cos(0) = 1 and sin(0) = 0 exactly in every libm, 2.9 * 1
+# and 2.9 * 0 are exact, and x is chosen as fl(fx - 2.9) with fl(x + 2.9) == fx
+# asserted (_search_actor), so fx is the authored value with or without a fused
+# multiply-add. Route coordinates lie within a factor of two of the axle's, so
+# fx - cx is exact too (Sterbenz); what is left is dx * dx + dy * dy and hypot.
+SEARCH_WHEELBASE = 2.9
+ACTOR_NB = 18        # cbev.hip: the circles a group holds (blocks of BP points)
+ACTOR_BATCH = 24     # cbev.hip: route points per lane and round of actor_search<1>
+BP = LY.ACB_PTS
+# g4 (32 slots; 528 points: 33 blocks, past the 32 candidate bits), narrow (64), wide (96)
+CAPS_SEARCH = (LY.Caps(16, 32, 528, 1), LY.Caps(16, 64, 320, 1), LY.Caps(16, 96, 320, 1))
+SEARCH_NACT = {32: (1, 2, 3, 5, 16, 17, 32), 64: (17, 33, 64), 96: (20, 40, 65, 80)}
+SEARCH_F = (600.0, 500.0)
+# the 20 integer lattice points at distance exactly 25
+LATTICE25 = tuple((sx * a, sy * b) for a, b in ((15, 20), (20, 15), (7, 24), (24, 7)) for sx in (1, -1)
+                  for sy in (1, -1)) + ((25, 0), (-25, 0), (0, 25), (0, -25))
+
+
+def max_route_coordinate(size):
+    """The largest coordinate of a route point on the render surface: pack_scene
+    itself checks no coordinate; a point past map + pad is past the padded map's
+    last texel (params.padded_map: the map blitted at (pad, pad) into a surface
+    of map + 2 pad), where nothing is drawn or looked up. (x, y) limits."""
+    P, _, _ = authored_world(size)
+    return P.map_w + P.pad, P.map_h + P.pad
+
+
+class SearchCase:
+    """One actor's search: route points, front axle, previous target index."""
+
+    def __init__(self, name, px, py, f, tid0):
+        self.name, self.fx, self.fy, self.tid0 = name, float(f[0]), float(f[1]), int(tid0)
+        self.px, self.py = np.asarray(px, np.float64), np.asarray(py, np.float64)
+        self.n = len(self.px)
+        assert self.n >= 2 and 0 <= self.tid0 <= self.n - 1
+
+    @property
+    def frozen(self):
+        return self.tid0 >= self.n - 1
+
+    def as_frozen(self):
+        return SearchCase(self.name + "/frozen", self.px, self.py, (self.fx, self.fy), self.n - 1)
+
+
+def expected_tidx(px, py, x, y, yaw, tid0):
+    """TIDX after one Actor.step, in float64 NumPy; a frozen actor keeps its own."""
+    if tid0 >= len(px) - 1:
+        return int(tid0)
+    fx = x + SEARCH_WHEELBASE * np.cos(yaw)
+    fy = y + SEARCH_WHEELBASE * np.sin(yaw)
+    return max(int(tid0), int(np.argmin(np.hypot(np.asarray(px) - fx, np.asarray(py) - fy))))
+
+
+def _filler(n, f, sgn=1.0):
+    """n route points far from the axle f (more than 700 px), all distances distinct."""
+    j = np.arange(n)
+    return f[0] + sgn * (500.0 + 2.0 * j), f[1] + sgn * (500.0 + (j % 3))
+
+
+def _case(name, n, special, tid0, f=SEARCH_F, sgn=1.0):
+    """A route of n filler points with the offsets special[i] = (dx, dy) from the axle at index i."""
+    px, py = _filler(n, f, sgn)
+    for i, (dx, dy) in special.items():
+        px[i], py[i] = f[0] + dx, f[1] + dy
+    return SearchCase(name, px, py, f, tid0)
+
+
+@lru_cache(maxsize=None)
+def near_tie_pairs(f=SEARCH_F, lim=None):
+    """((near), (far)) route points whose float64 squared distances from f differ
+    by 3e-14 to 1e-9 relative (above the 1e-14 band of the hypot pass and the
+    one-ulp difference a fused multiply-add makes; far below float32), and whose
+    float32 copies order them the other way round or not at all, with and
+    without a fused multiply-add in the float32 sum. Decimal coordinates k + 0.1
+    m on the circle of radius 0.5 (0.3, 0.4): equal in exact arithmetic, apart
+    by the float64 rounding of the coordinates."""
+    import itertools
+    f32 = np.float32
+    pts = sorted({(round(f[0] + sa * u, 1), round(f[1] + sb * v, 1)) for a, b in ((0.3, 0.4), (0.5, 0.0))
+                  for sa in (1, -1) for sb in (1, -1) for u, v in ((a, b), (b, a))})
+    if lim is not None:
+        pts = [p for p in pts if p[0] <= lim[0] and p[1] <= lim[1]]
+
+    def d64(p):
+        dx, dy = f[0] - p[0], f[1] - p[1]
+        return dx * dx + dy * dy
+
+    def d32(p, fma):
+        dx, dy = f32(f[0]) - f32(p[0]), f32(f[1]) - f32(p[1])
+        return f32(float(dx) * float(dx) + float(f32(dy * dy))) if fma else f32(f32(dx * dx) + f32(dy * dy))
+
+    out = []
+    for p, q in itertools.combinations(pts, 2):
+        a, b = d64(p), d64(q)
+        if a == b or not 3e-14 <= abs(a - b) / a <= 1e-9:
+            continue
+        near, far = (p, q) if a < b else (q, p)
+        if all(d32(near, m) >= d32(far, m) for m in (False, True)):
+            out.append((near, far))
+    return tuple(out)
+
+
+@lru_cache(maxsize=None)
+def hypot_pairs(count=4):
+    """(collapsing, separate): offsets ((dx_i, dy_i), (dx_j, dy_j)) from the axle,
+    multiples of 2^-18 px, with d2_j = d2_i - one ulp and both squared distances
+    exact in float64: a = 2 b + 3, (a, b) and (a - 1, b + 2) give a^2 + b^2 = N
+    and N - 1 (5 b^2 + 12 b + 9 and one less), with N in [2^52, 2^53), so the
+    integers are the float64 significands. collapsing: np.hypot (and the
+    correctly rounded square root of the exact sum) gives both the same distance,
+    so np.argmin keeps i; separate: the distances differ and j wins."""
+    s = 2.0 ** -18
+    col, sep = [], []
+    b = 30_100_003
+    while len(col) < count or len(sep) < count:
+        a = 2 * b + 3
+        N = a * a + b * b
+        assert 2 ** 52 <= N - 1 and N < 2 ** 53
+        pi, pj = (a * s, b * s), ((a - 1) * s, (b + 2) * s)
+        assert pi[0] * pi[0] + pi[1] * pi[1] == N * s * s and pj[0] * pj[0] + pj[1] * pj[1] == (N - 1) * s * s
+        hi, hj = np.hypot(*pi), np.hypot(*pj)
+        # the library's hypot agrees with the square root of the exact sum on these
+        assert hi == math.sqrt(N * s * s) and hj == math.sqrt((N - 1) * s * s)
+        (col if hi == hj else sep).append((pi, pj))
+        b += 700_001
+    return tuple(col[:count]), tuple(sep[:count])
+
+
+@lru_cache(maxsize=None)
+def search_cases():
+    """The scenario library: one SearchCase per searched situation (see DESIGN.md
+    section 4 for the table)."""
+    L = LATTICE25
+    A, B, C3, D4 = L[16], L[0], L[2], L[5]  # (25, 0), (15, 20), (15, -20), (-20, 15): all at distance 25
+    out = []
+    add = out.append
+    # exact ties of two points: the lower index wins
+    add(_case("tie/one-lane", 40, {3: A, 11: B}, 0))           # 8 apart: one lane's share for AW <= 8
+    add(_case("tie/two-lanes", 40, {3: A, 4: B}, 0))           # neighbours: two lanes for AW >= 2
+    add(_case("tie/window-blocks", 40, {3: A, 19: B}, 0))      # blocks 0 and 1 of the window
+    add(_case("tie/window-blocks-late", 96, {52: A, 77: B}, 50))
+    add(_case("tie/outside-earlier", 96, {5: A, 60: B}, 50))   # block 0 behind the window (blocks 3, 4): stays at 50
+    add(_case("tie/outside-earlier-near", 96, {40: A, 60: B}, 50))
+    add(_case("tie/outside-later", 96, {7: A, 70: B}, 2))      # block 4 ahead of the window (blocks 0, 1)
+    add(_case("tie/outside-later-far", 200, {20: A, 190: B}, 3))
+    add(_case("tie/outside-both", 200, {100: A, 190: B}, 3))   # both in blocks of the second round
+    # exact k-way ties
+    add(_case("tie3", 40, {3: A, 12: B, 21: C3}, 0))
+    add(_case("tie3/one-lane", 64, {2: A, 18: B, 34: C3}, 0))
+    add(_case("tie5/one-lane", 40, {1: A, 5: B, 9: C3, 13: D4, 17: L[9]}, 0))
+    add(_case("tie5/blocks", 80, {1: A, 17: B, 33: C3, 49: D4, 65: L[9]}, 0))
+    add(_case("tie4/behind", 80, {1: A, 5: B, 9: C3, 13: D4}, 60))
+    order = [L[(7 * k + 3) % 20] for k in range(20)]            # a fixed shuffle of the 20 points
+    add(SearchCase("tie20", [SEARCH_F[0] + p[0] for p in order], [SEARCH_F[1] + p[1] for p in order], SEARCH_F, 0))
+    # the first of the 20 at index 17: no lane of a group of 16 or fewer visits it first
+    add(_case("tie20/offset", 48, {17 + k: p for k, p in enumerate(order)}, 0))
+    add(_case("tie20/offset-tid", 48, {17 + k: p for k, p in enumerate(order)}, 20))
+    # near-ties that float32 cannot separate, the nearer point at the lower and at the higher index
+    for k, (near, far) in enumerate(near_tie_pairs()[:6]):
+        rel = lambda p: (p[0] - SEARCH_F[0], p[1] - SEARCH_F[1])  # noqa: E731
+        i, j = ((3, 11), (3, 4), (6, 22), (5, 40), (2, 10), (9, 12))[k]
+        add(_case(f"near{k}/low", 48, {i: rel(near), j: rel(far)}, 0))
+        add(_case(f"near{k}/high", 48, {i: rel(far), j: rel(near)}, 0))
+        out[-2].px[i], out[-2].py[i], out[-2].px[j], out[-2].py[j] = near[0], near[1], far[0], far[1]
+        out[-1].px[i], out[-1].py[i], out[-1].px[j], out[-1].py[j] = far[0], far[1], near[0], near[1]
+    # the hypot collapse: j is nearer by one ulp of the squared distance
+    col, sep = hypot_pairs()
+    for k, (pi, pj) in enumerate(col):
+        i, j = ((4, 9), (4, 5), (7, 23), (2, 50))[k]
+        add(_case(f"collapse{k}", 64, {i: pi, j: pj}, 0))
+    for k, (pi, pj) in enumerate(sep):
+        i, j = ((4, 9), (4, 5), (7, 23), (2, 50))[k]
+        add(_case(f"separate{k}", 64, {i: pi, j: pj}, 0))
+    # route lengths: the minimum on the last point, and a tie of the last two
+    lengths = [2, 3, BP - 1, BP, BP + 1, 2 * BP, 2 * BP + 1, ACTOR_BATCH - 1, ACTOR_BATCH, ACTOR_BATCH + 1,
+               BP * ACTOR_NB, BP * ACTOR_NB + 1, BP * (ACTOR_NB + 1), BP * (ACTOR_NB + 2), BP * 22, BP * 26, BP * 32 + 1, BP * 33]
+    for n in lengths:
+        add(_case(f"len{n}/last", n, {n - 1: A}, 0))
+        add(_case(f"len{n}/tie-last-two", n, {n - 2: A, n - 1: B}, 0))
+        if n > 2 * BP:
+            add(_case(f"len{n}/tie-first-last", n, {1: A, n - 1: B}, 0))
+            add(_case(f"len{n}/behind", n, {1: A}, n - 5))
+    # the previous target index: the window's clamp at both ends
+    for t in (0, 1, 2, 3, 62, 63):
+        add(_case(f"tid{t}/ahead", 64, {40: A}, t))
+        add(_case(f"tid{t}/tie", 64, {6: A, 45: B}, t))
+    for t in (17, 18, 19, 33, 34, 35):  # tid0 - 2 crosses a block boundary
+        add(_case(f"tid{t}/edge", 80, {t - 3: A, t + 20: B}, t))
+    add(_case("behind/far", 200, {10: A}, 150))       # many blocks behind the window: stays at 150
+    add(_case("behind/far-tie", 200, {10: A, 160: B}, 150))
+    add(_case("behind/near-window", 200, {130: A}, 150))
+    add(_case("ahead/far", 200, {180: A}, 5))         # many blocks ahead: the second round finds it
+    add(_case("ahead/far-304", 304, {300: A}, 5))
+    add(_case("ahead/window-decoy", 200, {8: (26.0, 0.0), 180: A}, 5))  # a point 1 px farther inside the window
+    # the largest coordinates a route point can take (size 256): a near-tie pair there
+    mx, my = max_route_coordinate(256)
+    fbig = (mx - 1.0, my - 1.0)
+    near, far = max(near_tie_pairs(fbig, (float(mx), float(my))), key=lambda pq: sum(pq[0]) + sum(pq[1]))
+    for tag, (p, q) in (("low", (near, far)), ("high", (far, near))):
+        c = _case(f"largest/{tag}", 48, {3: (0.0, 0.0), 11: (0.0, 0.0)}, 0, f=fbig, sgn=-1.0)
+        c.px[3], c.py[3], c.px[11], c.py[11] = p[0], p[1], q[0], q[1]
+        add(c)
+    assert len({c.name for c in out}) == len(out)
+    return tuple(out)
+
+
+def search_width(actor_cap, nact, slot):
+    """(AW, windowed) of actor `slot` in an env of nact actors (cbev.hip
+    actors_body): AW 0 is the serial path of more than 64 actors."""
+    if actor_cap > 64 and nact > 64:
+        return 0, False
+    minaw = 4 if actor_cap <= 32 else 1
+    aw = 64 if nact <= 1 else 32 if nact <= 2 else 16 if nact <= 4 else 8 if nact <= 8 else 4 if nact <= 16 \
+        else 2 if nact <= 32 else 1
+    aw = max(minaw, aw)
+    if aw == 4 and nact > 16 and slot >= 16:
+        aw = 8 if nact <= 24 else 4
+    return aw, aw > 1
+
+
+SEARCH_CLASSES = ("window_only", "outside_scanned", "all", "all_cq", "all_nb32", "lane3", "hypot_collapse", "never_back",
+                  "tie_one_lane", "tie_two_lanes", "tie_window_blocks", "tie_outside_earlier", "tie_outside_later",
+                  "unwindowed", "serial", "frozen")
+
+
+def search_classes(c, aw, windowed):
+    """The branch classes one search falls into: cbev.hip actor_search_win<AW> /
+    actor_search<AW> restated with NumPy float32 (no fused multiply-add: the
+    cases keep every predicate far from its threshold or exactly on it, see
+    near_tie_pairs). Coverage accounting only, never an expected index."""
+    if c.frozen:
+        return {"frozen"}
+    if aw == 0:
+        return {"serial"}
+    f32 = np.float32
+    n, out = c.n, set()
+    cf = np.stack([c.px, c.py], 1).astype(f32)
+    dx, dy = f32(c.fx) - cf[:, 0], f32(c.fy) - cf[:, 1]
+    d = dx * dx + dy * dy
+    nb = (n + BP - 1) // BP
+    blk = np.arange(n) // BP
+    if windowed:
+        kb = min(max(c.tid0 - 2, 0) // BP, max(nb - 2, 0))
+        w0, w1 = kb * BP, min(kb * BP + 2 * BP, n)
+        inwin = (np.arange(n) >= w0) & (np.arange(n) < w1)
+        cq = (ACTOR_NB + aw - 1) // aw
+        if nb > cq * aw or nb > 32:
+            out.add("all")
+            out.add("all_nb32" if nb > 32 else "all_cq")
+            scanned = np.ones(n, bool)
+        else:
+            reach = np.sqrt(d[inwin].min()) + f32(0.15) + f32(0.05)
+            circ = LY.acb_circles(cf)
+            cand = set()
+            for k in range(nb):
+                if k in (kb, kb + 1):
+                    continue
+                bx = f32((int(circ[k, 0]) & 0xFFFF) - 32768) * f32(0.125)
+                by = f32((int(circ[k, 0]) >> 16) - 32768) * f32(0.125)
+                ex, ey = f32(c.fx) - bx, f32(c.fy) - by
+                if np.sqrt(ex * ex + ey * ey) - f32(circ[k, 1]) * f32(0.125) <= reach:
+                    cand.add(k)
+            out.add("outside_scanned" if cand else "window_only")
+            scanned = inwin | np.isin(blk, list(cand))
+        if aw >= 32:
+            lane = np.where(inwin, np.arange(n) - w0, np.arange(n) % BP)
+        else:
+            lane = np.arange(n) % aw
+    else:
+        out.add("unwindowed")
+        w0, w1 = 0, n
+        inwin = np.ones(n, bool)
+        scanned, lane = np.ones(n, bool), np.arange(n) % aw
+    thr = (np.sqrt(d[scanned].min()) + f32(0.15)) ** 2
+    hits = scanned & (d <= thr)
+    if np.bincount(lane[hits], minlength=64).max() >= 3:
+        out.add("lane3")
+    ex, ey = c.fx - c.px, c.fy - c.py
+    d2 = ex * ex + ey * ey
+    amin = int(np.argmin(np.hypot(ex, ey)))
+    if int(np.argmin(d2)) != amin:
+        out.add("hypot_collapse")
+    if amin < c.tid0:
+        out.add("never_back")
+    tie = np.flatnonzero(d2 == d2.min())
+    if len(tie) >= 2:
+        i, j = int(tie[0]), int(tie[1])
+        if scanned[i] and scanned[j]:
+            out.add("tie_one_lane" if lane[i] == lane[j] else "tie_two_lanes")
+        if windowed:
+            if inwin[i] and inwin[j] and blk[i] != blk[j]:
+                out.add("tie_window_blocks")
+            if i < w0 and inwin[j]:
+                out.add("tie_outside_earlier")
+            if inwin[i] and j >= w1:
+                out.add("tie_outside_later")
+    return out
+
+
+def _search_actor(view, slot, c):
+    """SearchCase c into actor slot `slot` of a packed record: the route as
+    authored (no smoothing), its float32 copy and circles as scene_pack writes
+    them, the actor at rest on yaw 0 with its front axle exactly on (fx, fy)."""
+    n = c.n
+    x = c.fx - SEARCH_WHEELBASE
+    assert x + SEARCH_WHEELBASE * 1.0 == c.fx, (c.name, "the front axle is not exact")
+    assert n <= view.acx.shape[1], (c.name, n)
+    view.acx[slot, :n], view.acy[slot, :n], view.acyaw[slot, :n] = c.px, c.py, 0.0
+    view.acf[slot, :n, 0], view.acf[slot, :n, 1] = view.acx[slot, :n], view.acy[slot, :n]
+    view.acb[slot] = 0
+    view.acb[slot, :(n + BP - 1) // BP] = LY.acb_circles(view.acf[slot, :n])
+    ad, ai = view.ad, view.ai
+    ad[LY.AD["X"], slot], ad[LY.AD["Y"], slot], ad[LY.AD["YAW"], slot], ad[LY.AD["V"], slot] = x, c.fy, 0.0, 0.0
+    assert ad[LY.AD["T_SPEED"], slot] == 0.0 and ad[LY.AD["CRUISE"], slot] == 0.0
+    ai[LY.AI["NROUTE"], slot], ai[LY.AI["TIDX"], slot] = n, c.tid0
+
+
+SEARCH_STEPS = 2
+
+
+def actor_search_batch(caps, size=128):
+    """(P, padded, caps, recs, layout, acts, cases): for every actor count of
+    SEARCH_NACT[caps.actor_cap], the scenario library (those whose route fits
+    caps.actor_route_cap) dealt into envs of that many actors, a frozen copy
+    (TIDX on the last point) after every third, so frozen actors sit between
+    live ones of one group round. cases[e] = [(slot, SearchCase, AW, windowed)].
+    The hero stands on its road, far from every actor; acts: nothing pressed."""
+    P, padded, _ = authored_world(size)
+    y, x0, x1 = _road_run(size)
+    ex, ey = x0 + 40, y
+    lib_ = [c for c in search_cases() if c.n <= caps.actor_route_cap]
+    deal = []
+    for k, c in enumerate(lib_):
+        deal.append(c)
+        if k % 3 == 2:
+            deal.append(c.as_frozen())
+    groups = []
+    for nact in SEARCH_NACT[caps.actor_cap]:
+        m = (len(deal) + nact - 1) // nact
+        for g in range(m):
+            groups.append([deal[(g * nact + a) % len(deal)] for a in range(nact)])
+    specs = [SceneSpec(agent_rx=[ex + 4 * i for i in range(8)], agent_ry=[ey] * 8, hero_jitter_seed=e,
+                       actor_jitter_seed=e, vehicles=[_still("vehicle", 10.0 + a, 10.0) for a in range(len(g))])
+             for e, g in enumerate(groups)]
+    recs, layout, views = pack_records(specs, size, caps)
+    cases = []
+    for v, g in zip(views, groups):
+        assert v.i("NACT") == len(g)
+        row = []
+        for slot, c in enumerate(g):
+            _search_actor(v, slot, c)
+            assert math.hypot(v.h("X") - c.fx, v.h("Y") - c.fy) > 100.0  # no collision, no actor state near the hero
+            row.append((slot, c) + search_width(caps.actor_cap, len(g), slot))
+        cases.append(row)
+    acts = np.zeros((SEARCH_STEPS, len(specs)), np.int32)
+    return P, padded, caps, recs, layout, acts, cases

@@ -114,10 +114,12 @@ class Fixture:
 
 
 @lru_cache(maxsize=None)
-def load() -> Fixture:
-    with np.load(os.path.join(GOLDEN, "episodes.npz"), allow_pickle=False) as z:
+def load(name="episodes") -> Fixture:
+    """The fixture `name`: "episodes" (whole episodes) or "ties" (make_golden_ties.py:
+    short authored cases on exact thresholds; they need not end)."""
+    with np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False) as z:
         arrays = {k: z[k] for k in z.files}
-    with open(os.path.join(GOLDEN, "episodes.json"), encoding="utf-8") as f:
+    with open(os.path.join(GOLDEN, name + ".json"), encoding="utf-8") as f:
         meta = json.load(f)
     return Fixture(arrays, meta)
 

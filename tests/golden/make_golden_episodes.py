@@ -355,8 +355,10 @@ def _actor_id(v):
     return 1, int(v)
 
 
-def run_episode(spec, seed):
-    """One episode of `spec` at `seed`: (record, (smallest near-tie margin, its name))."""
+def run_episode(spec, seed, margin_fn=None):
+    """One episode of `spec` at `seed`: (record, (smallest near-tie margin, its name)).
+    margin_fn(env, info): what measures a step's margin instead of step_margin
+    (make_golden_ties.py records its named margins through it)."""
     env = make_env(spec["config"])
     options = dict(spec.get("options", {}))
     tmp = None
@@ -387,7 +389,7 @@ def run_episode(spec, seed):
         ROUND_LOG.margin = math.inf
         _, reward, terminated, truncated, info_out = env.step(action)
         info = env.current_info
-        margin = min(margin, step_margin(env, info))
+        margin = min(margin, (margin_fn or step_margin)(env, info))
         kind, aid = _actor_id(info["collision"]["actor_id"])
         sticky = info_out["episode_info"]["termination"] if terminated else env.stats.current.cause
         h = info["hero"]

@@ -18,6 +18,7 @@ from carlabev_env_amd._lib import OBS_BITS, OBS_F16, OBS_F32, OBS_U8, check, lib
 from gpu_harness import (P_, DevWorld, EpisodeStatsOn, assert_same, error_flags, make_lanes, out_bufs,
                          preview_counts, ptr, reset_counts, reset_terminated_all, set_term, step_all, term_of)
 from helpers import CAPS_FULL, action_stream, bench_caps, build_records, world
+import episode_fixture as EF
 
 
 # ---------------------------------------------------------------------- the device against the oracle
@@ -506,3 +507,104 @@ def cout(kind, F, C):
 
 def out_bytes(dt, n, Cout, P):
     return n * Cout * {"float32": 4 * P, "float16": 2 * P, "uint8": P, "bits": (P + 7) // 8}[dt]
+
+
+# ---------------------------------------------------------------------- the device against a recorded fixture
+LIBM = 1e-9            # device libm against glibc / NumPy (test_gpu_parity.py's bar)
+F32_ULP = 2.0 ** -23
+
+
+def summary_of_row(row):
+    """The fields of an episode summary row (CBEV_EP_FIELDS) under the fixture's names."""
+    E = LY.EP
+    return {"return": row[E["RETURN"]], "length": row[E["LENGTH"]], "mean_speed": row[E["MEAN_SPEED"]],
+            "mean_abs_accel_long": row[E["MEAN_ABS_AL"]], "mean_abs_accel_lat": row[E["MEAN_ABS_ALAT"]],
+            "mean_abs_jerk_long": row[E["MEAN_ABS_JL"]], "mean_abs_jerk_lat": row[E["MEAN_ABS_JLAT"]],
+            "mean_abs_yaw_rate": row[E["MEAN_ABS_YR"]], "mean_abs_yaw_acc": row[E["MEAN_ABS_YACC"]],
+            "comfort_violation_rate": row[E["VIOL_RATE"]], "harsh_brake_rate": row[E["HARSH_RATE"]],
+            "num_vehicles": row[E["NUM_VEH"]], "len_ego_route": row[E["LEN_ROUTE_M"]]}
+
+
+def fixture_info(ep, t):
+    """cbev_step's per-step float32 export (include/cbev.h) from a fixture episode."""
+    M = ep._fx.meta
+    o = np.zeros(16, np.float64)
+    o[0:7], o[7:11] = ep.comfort[t], ep.control[t]
+    o[11], o[12] = ep.reward[t], ep.dist2wp[t]
+    o[13], o[14], o[15] = ep.tile[t], LY.COLL[M["coll_names"][int(ep.collided[t])]], ep.n_actors_state[t]
+    return o.astype(np.float32)
+
+
+def replay_on_device(eps, split, ends=True):
+    """The fixture episodes `eps` (one configuration) as one batch in one context
+    through cbev_reset and cbev_step with the device episode statistics on,
+    compared with the fixture directly after the reset and after every step: the
+    records (episode_fixture.compare_step), reward / term / trunc / cause / info
+    and, with ends (whole episodes, which end on their last step), the summary
+    row at an env's terminal step. An env is compared up to its last recorded
+    step and ignored afterwards. split: cbev_set_split_step's argument, or None
+    for the context's default. Returns (env-steps compared, Deviation)."""
+    n = len(eps)
+    P, padded = EF.world_of(eps[0].config)
+    caps = CAPS_FULL
+    layout = LY.Layout.make(caps)
+    recs = np.zeros((n, layout.record_bytes), np.uint8)
+    for e, ep in enumerate(eps):
+        need = ep.scene_spec().caps_needed()
+        assert all(a <= b for a, b in zip(need, (caps.route_cap, caps.actor_cap, caps.actor_route_cap, caps.tl_cap))), need
+        recs[e], _, _ = EF.pack_episode(ep, caps)
+    L = lib()
+    dw = DevWorld(P, padded, caps)
+    if split is not None:
+        check(L.cbev_set_split_step(dw.ctx, split), "split_step")
+    S = P.size
+    d_recs = torch.from_numpy(recs).cuda()
+    frames = torch.zeros((n, S, S), dtype=torch.uint8, device="cuda")
+    check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(frames), 1, None), "reset")
+    stats = EpisodeStatsOn(dw.ctx, n)
+    torch.cuda.synchronize()
+    dev = EF.Deviation(libm=LIBM, actor_yaw_mod=True)
+    h = d_recs.cpu().numpy()
+    for e, ep in enumerate(eps):
+        EF.compare_reset(ep, LY.RecordView(h[e], layout), dev, None)
+    rew, term, trunc, cause, info = out_bufs(n).values()
+    cont = P.action_kind == 1
+    compared = rows_seen = 0
+    for t in range(max(ep.n_steps for ep in eps)):
+        live = [e for e, ep in enumerate(eps) if t < ep.n_steps]
+        acts = np.zeros((n, 3), np.float32) if cont else np.zeros(n, np.int32)  # finished envs: nothing pressed
+        for e in live:
+            acts[e] = eps[e].action(t)
+        a = torch.from_numpy(acts).cuda()
+        check(L.cbev_step(dw.ctx, ptr(d_recs), n, ptr(a), ptr(frames), ptr(rew), ptr(term), ptr(trunc), ptr(cause),
+                          ptr(info), None), "step")
+        torch.cuda.synchronize()
+        h = d_recs.cpu().numpy()
+        h_rew, h_term, h_trunc = rew.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy()
+        h_cause, h_info = cause.cpu().numpy(), info.cpu().numpy()
+        slot = t % stats.RING
+        rows = stats.rows[slot, :int(stats.counts[slot].item())].cpu().numpy()
+        by_env = {int(r[LY.EP["ENV"]]): r for r in rows}
+        for e in live:
+            ep, tag = eps[e], (eps[e].name, t)
+            EF.compare_step(ep, t, LY.RecordView(h[e], layout), int(h_cause[e]), dev)
+            dev.check("reward", [h_rew[e]], [ep.reward[t]], tag + ("reward output",))
+            assert h_term[e] == ep.terminated[t] and h_trunc[e] == ep.truncated[t], tag + ("term, trunc outputs",)
+            want = fixture_info(ep, t)
+            assert np.array_equal(h_info[e, 13:], want[13:]), tag + ("info ints", h_info[e, 13:], want[13:])
+            assert np.all(np.abs(h_info[e, :13].astype(np.float64) - want[:13]) <=
+                          EF.BOUND["reward"][0] + LIBM + F32_ULP * np.abs(want[:13])), tag + ("info", h_info[e], want)
+            if ep.terminated[t]:
+                assert e in by_env, tag + ("no summary row at the terminal step",)
+                row = by_env[e]
+                assert row[LY.EP["EPISODE"]] == 0, tag
+                if ends:
+                    EF.compare_summary(ep, summary_of_row(row), int(row[LY.EP["CAUSE"]]), dev)
+                rows_seen += 1
+            else:
+                assert e not in by_env, tag + ("a summary row before the terminal step",)
+            compared += 1
+    assert compared == sum(ep.n_steps for ep in eps)
+    assert rows_seen == (n if ends else sum(int(ep.terminated[-1]) for ep in eps))
+    assert error_flags(dw.ctx) == 0
+    return compared, dev

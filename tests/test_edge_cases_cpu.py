@@ -324,3 +324,113 @@ def test_retreat_routes_equal_host_smoothing(caps):
             orc.step_one(recs[e], np.ascontiguousarray(acts[t, e]), None)
     states = [int(views[e].ai[LY.AI["BSTATE"], s]) for e, cs in enumerate(cases) for s, _, _ in cs]
     assert states.count(LY.BSTATE["retreated"]) >= 10 and states.count(LY.BSTATE["retreating"]) >= 3, states
+
+
+# ------------------------------------------------------------------ the actor target search
+SEARCH_IDS = [f"slots{c.actor_cap}" for c in EC.CAPS_SEARCH]
+_NO_SERIAL = "at most 64 actor slots: no env holds more than 64 actors, so none takes the serial d_actor_step"
+_NO_AW1 = ("k_actors_g4 compiles no group narrower than 4 lanes: 17 to 32 actors take two passes of actor_search_win, "
+           "never the unwindowed actor_search<1>")
+_NB20 = ("routes of at most 320 points: 20 blocks; only the 2-lane groups (more than 18 blocks) scan every block, "
+         "the 32 candidate bits are never exceeded")
+SEARCH_EXCLUDED = {32: {"serial": _NO_SERIAL, "unwindowed": _NO_AW1}, 64: {"serial": _NO_SERIAL, "all_nb32": _NB20},
+                   96: {"all_nb32": _NB20}}
+
+
+@pytest.mark.parametrize("caps", EC.CAPS_SEARCH, ids=SEARCH_IDS)
+def test_actor_search_oracle_equals_argmin_and_covers_every_class(caps):
+    """Every actor of the directed search matrix (EC.actor_search_batch): the
+    oracle's AI_TIDX after one step is max(tid0, argmin hypot) in float64 NumPy,
+    a frozen actor's is unchanged, the actor has not moved, and a second step
+    from the chosen index chooses it again. The branch classes the kernel's
+    search takes over these cases (EC.search_classes) are counted."""
+    P, padded, caps, recs, layout, acts, cases = EC.actor_search_batch(caps)
+    orc = O.Oracle(P, padded, caps.c(), layout.record_bytes)
+    hist, widths = collections.Counter(), collections.Counter()
+    AD, AI = LY.AD, LY.AI
+    for e, row in enumerate(cases):
+        v = LY.RecordView(recs[e], layout)
+        pose = v.ad[[AD["X"], AD["Y"], AD["YAW"]]].copy()
+        want = {}
+        for slot, c, aw, windowed in row:
+            n = int(v.ai[AI["NROUTE"], slot])
+            want[slot] = EC.expected_tidx(v.acx[slot, :n], v.acy[slot, :n], *pose[:, slot], int(v.ai[AI["TIDX"], slot]))
+            assert (pose[0, slot] + 2.9 * np.cos(pose[2, slot]), pose[1, slot]) == (c.fx, c.fy), (c.name, "front axle")
+            hist.update(EC.search_classes(c, aw, windowed))
+            widths[aw] += not c.frozen
+            if c.frozen:
+                assert want[slot] == c.n - 1
+        for t in range(EC.SEARCH_STEPS):
+            orc.step_one(recs[e], np.ascontiguousarray(acts[t, e]), None)
+            for slot, c, aw, windowed in row:
+                assert v.ai[AI["TIDX"], slot] == want[slot], (e, slot, c.name, aw, t, int(v.ai[AI["TIDX"], slot]), want[slot])
+            assert np.array_equal(v.ad[[AD["X"], AD["Y"], AD["YAW"]]], pose), (e, t, "an actor moved")
+        assert v.i("TERM") == 0 and v.i("COLLIDED") == 0
+    print(f"\nslots {caps.actor_cap}, {len(recs)} envs:", {k: hist.get(k, 0) for k in EC.SEARCH_CLASSES}, "AW", dict(widths))
+    excluded = SEARCH_EXCLUDED[caps.actor_cap]
+    for k in EC.SEARCH_CLASSES:
+        if k in excluded:
+            assert hist.get(k, 0) == 0, (k, "is reached after all: take it off the exclusions table")
+        else:
+            assert hist.get(k, 0) >= 3, (caps, k, hist.get(k, 0))
+    want_aw = {32: {64, 32, 16, 8, 4}, 64: {2, 1}, 96: {2, 1, 0}}[caps.actor_cap]
+    assert {aw for aw, m in widths.items() if m >= 3} == want_aw, widths
+
+
+def test_actor_search_cases_are_what_they_claim():
+    """The scenario library's own claims, from float64 NumPy alone: exact ties are
+    exact, near-ties are ordered the other way round in float32, the hypot pairs
+    collapse or not, and every coordinate is below the kernel's 4096 px bound."""
+    for size in (64, 128, 256):
+        assert max(EC.max_route_coordinate(size)) < 4096, size  # cbev.hip actor_search: "coordinates below 4096 px"
+    assert EC.max_route_coordinate(256) == (2411, 2923)
+    by = {c.name: c for c in EC.search_cases()}
+    d2 = lambda c: (c.fx - c.px) ** 2 + (c.fy - c.py) ** 2  # noqa: E731
+    for name, c in by.items():
+        assert np.abs(c.px).max() < 4096 and np.abs(c.py).max() < 4096, name
+        if name.startswith("tie") and not name.startswith("tid"):
+            k = int(name[3:].split("/")[0] or 2)
+            assert np.count_nonzero(d2(c) == d2(c).min()) == k, name
+    assert sorted(np.flatnonzero(d2(by["tie20/offset"]) == 625.0)) == list(range(17, 37))
+    col = [c for n, c in by.items() if n.startswith("collapse")]
+    sep = [c for n, c in by.items() if n.startswith("separate")]
+    assert len(col) >= 3 and len(sep) >= 3
+    for c in col + sep:
+        h = np.hypot(c.fx - c.px, c.fy - c.py)
+        i, j = np.argsort(d2(c), kind="stable")[:2][::-1]  # j is nearer by one ulp of d2
+        assert i < j and d2(c)[j] < d2(c)[i] and np.nextafter(d2(c)[j], np.inf) == d2(c)[i], c.name
+        assert (h[i] == h[j]) == (c in col) and int(np.argmin(h)) == (i if c in col else j), c.name
+    near = [c for n, c in by.items() if n.startswith("near") or n.startswith("largest")]
+    assert len(near) >= 8
+    for c in near:
+        i, j = np.argsort(d2(c))[:2]
+        rel = (d2(c)[j] - d2(c)[i]) / d2(c)[i]
+        assert 3e-14 <= rel <= 1e-9, (c.name, rel)
+        cf = np.stack([c.px, c.py], 1).astype(np.float32)
+        f = (np.float32(c.fx) - cf[:, 0]) ** 2 + (np.float32(c.fy) - cf[:, 1]) ** 2
+        assert f[i] >= f[j], (c.name, "float32 separates the pair the right way round")
+        assert (i < j) == c.name.endswith("low")
+    big = by["largest/low"]
+    assert 2410 <= big.px.max() < 2411 and 2922 <= big.py.max() < 2923  # within a pixel of the limit on both axes
+
+
+def test_search_restatement_holds_the_kernel_constants():
+    """edge_cases.py's copies of the search's constants and of actors_body's group
+    widths, read back from cbev.hip: a kernel change that moves them fails here
+    instead of letting the coverage accounting drift."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(LY.HEADER), "..", "carlabev_env_amd", "csrc", "cbev.hip")).read()
+    const = lambda name: int(re.search(rf"constexpr int {name} = (\d+);", src).group(1))  # noqa: E731
+    assert (const("ACTOR_NB"), const("ACTOR_BATCH")) == (EC.ACTOR_NB, EC.ACTOR_BATCH)
+    assert "return (ACTOR_NB + aw - 1) / aw; }" in src and "nb > ACTOR_CQ * AW || nb > 32" in src
+    assert "sqrtf(mw) + 0.15f + 0.05f" in src and src.count("sqrtf(mf) + 0.15f, thr = tf * tf") == 2
+    # actors_body: the width table, the two-pass split of 17-32 actors, the capacity classes
+    flat = " ".join(src.split())
+    assert ("max(MINAW, nact <= 1 ? 64 : nact <= 2 ? 32 : nact <= 4 ? 16 : nact <= 8 ? 8 : nact <= 16 ? 4 : nact <= 32 ? 2 "
+            ": 1)") in flat
+    assert "const int b2 = nact <= 24 ? actor_search_win<8>(r, 16, nact," in flat and "if (WIDE && nact > 64)" in flat
+    assert "C.actor_cap > 64 ? k_actors<true, 1> : C.actor_cap > 32 ? k_actors<false, 1> : k_actors_g4" in flat
+    assert EC.search_width(32, 20, 17) == (8, True) and EC.search_width(32, 30, 17) == (4, True)
+    assert EC.search_width(64, 20, 3) == (2, True) and EC.search_width(64, 40, 3) == (1, False)
+    assert EC.search_width(96, 70, 3) == (0, False)

@@ -7,6 +7,10 @@ test_edge_cases_cpu.py.
 Same bar as test_gpu_parity.py (run_parity): reset and step frames, whole
 records, flags, rewards and info after every step, and no error flag at the end
 (no CBEV_ERR_RASTER_WINDOW).
+
+The actor target search matrix (EC.actor_search_batch) is held to the float64
+NumPy statement as well: every actor's AI_TIDX is an integer run_parity
+compares exactly, and the oracle's equals max(tid0, argmin hypot) on the CPU.
 """
 from __future__ import annotations
 
@@ -20,7 +24,8 @@ torch = pytest.importorskip("torch")
 import edge_cases as EC
 from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import lib
-from gpu_harness import error_flags, make_lanes, step_all
+from carlabev_env_amd._lib import check
+from gpu_harness import assert_same_state, error_flags, make_lanes, reset_counts, step_all, step_repeat
 from gpu_scenes import cached_bank_frames_match_render, run_parity
 
 pytestmark = pytest.mark.gpu
@@ -184,3 +189,57 @@ def test_retreats_at_pinned_route_lengths(caps):
     _run(P, padded, caps, recs, acts, on_step=on_step)
     assert seen["state"] == {LY.BSTATE["retreating"]}
     assert set(seen["nroute"]) == set(range(2, 14)) | {32, 63, 64}
+
+
+@pytest.mark.parametrize("caps", EC.CAPS_SEARCH, ids=[f"slots{c.actor_cap}" for c in EC.CAPS_SEARCH])
+def test_actor_target_search_matrix(caps):
+    """calc_target_index at its edges: exact ties, near-ties float32 cannot
+    separate, the hypot collapse, route lengths around every block and batch
+    boundary, the window's clamp, minima far behind and far ahead of the window,
+    1 to 80 actors with frozen ones in between. 32, 64 and 96 actor slots:
+    k_actors_g4 at every group width, k_actors<false, 1> (2 lanes and the
+    unwindowed actor_search<1>), k_actors<true> (the serial path). Two steps: the
+    second searches from the index the first chose. Every actor's TIDX after
+    each step is the float64 NumPy arg-min's."""
+    P, padded, caps, recs, layout, acts, cases = EC.actor_search_batch(caps)
+    AD, AI = LY.AD, LY.AI
+    want = []
+    for e, row in enumerate(cases):
+        v = LY.RecordView(recs[e], layout)
+        want.append({slot: EC.expected_tidx(v.acx[slot, :c.n], v.acy[slot, :c.n], v.ad[AD["X"], slot], v.ad[AD["Y"], slot],
+                                            v.ad[AD["YAW"], slot], c.tid0) for slot, c, _, _ in row})
+    seen = []
+
+    def on_step(t, views, causes):  # the oracle's records, which the device's equal (actor ints exactly)
+        for e, (v, row) in enumerate(zip(views, cases)):
+            for slot, c, aw, _ in row:
+                assert v.ai[AI["TIDX"], slot] == want[e][slot], (t, e, slot, c.name, aw, int(v.ai[AI["TIDX"], slot]))
+        seen.append(t)
+
+    assert _run(P, padded, caps, recs, acts, on_step=on_step) == 0
+    assert seen == list(range(EC.SEARCH_STEPS))
+
+
+def test_actor_target_search_under_repeat():
+    """The 32-slot matrix through cbev_step_repeat(k = 2) (k_actors_g4_rep: the
+    gated body sees the same ties) against two plain steps: records, frame,
+    outputs (rewards summed), statistics and reset counts equal bit for bit."""
+    P, padded, caps, recs, layout, acts, cases = EC.actor_search_batch(EC.CAPS_SEARCH[0])
+    n, L = len(recs), lib()
+    A, B = make_lanes(P, padded, caps, recs, None, 1, [{}, {}])
+    a = torch.from_numpy(np.ascontiguousarray(acts[0])).cuda()
+    check(step_repeat(L, A.dw, A.recs, n, a, 2, A.ring[0], A.out), "step_repeat")
+    rsum = torch.zeros(n, dtype=torch.float64, device="cuda")
+    for t in range(2):
+        step_all([B], acts[t], 0)
+        assert not B.out["term"].any()
+        rsum = rsum + B.out["rew"]
+    B.out["rew"].copy_(rsum)
+    torch.cuda.synchronize()
+    assert_same_state(A, B, 0, n, counts_a=reset_counts(L, A.dw, n), counts_b=reset_counts(L, B.dw, n))
+    assert error_flags(A.dw.ctx) == 0 and error_flags(B.dw.ctx) == 0
+    got = A.recs.cpu().numpy()
+    for e, row in enumerate(cases):
+        v = LY.RecordView(got[e], layout)
+        for slot, c, _, _ in row:
+            assert v.ai[LY.AI["TIDX"], slot] == EC.expected_tidx(c.px, c.py, c.fx - EC.SEARCH_WHEELBASE, c.fy, 0.0, c.tid0)

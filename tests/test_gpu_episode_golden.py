@@ -19,114 +19,24 @@ two doubles 1e-9 apart round to the same float32 or to neighbours).
 """
 from __future__ import annotations
 
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import episode_fixture as EF
-from carlabev_env_amd import layout as LY
-from carlabev_env_amd._lib import check, lib
-from episode_fixture import BOUND, Deviation, compare_reset, compare_step, compare_summary, pack_episode, world_of
-from gpu_harness import DevWorld, EpisodeStatsOn, error_flags, out_bufs, ptr
-from helpers import CAPS_FULL
+from gpu_scenes import replay_on_device
 
 pytestmark = pytest.mark.gpu
-
-LIBM = 1e-9            # device libm against glibc / NumPy (test_gpu_parity.py's bar)
-F32_ULP = 2.0 ** -23
 
 # (configuration, cbev_set_split_step argument or None for the context's default)
 RUNS = [("carl128", 1), ("carl128", 0), ("shaping128c", None), ("short128", None), ("carl256", None), ("carl64", None)]
 
 
-def summary_of_row(row):
-    """The fields of an episode summary row (CBEV_EP_FIELDS) under the fixture's names."""
-    E = LY.EP
-    return {"return": row[E["RETURN"]], "length": row[E["LENGTH"]], "mean_speed": row[E["MEAN_SPEED"]],
-            "mean_abs_accel_long": row[E["MEAN_ABS_AL"]], "mean_abs_accel_lat": row[E["MEAN_ABS_ALAT"]],
-            "mean_abs_jerk_long": row[E["MEAN_ABS_JL"]], "mean_abs_jerk_lat": row[E["MEAN_ABS_JLAT"]],
-            "mean_abs_yaw_rate": row[E["MEAN_ABS_YR"]], "mean_abs_yaw_acc": row[E["MEAN_ABS_YACC"]],
-            "comfort_violation_rate": row[E["VIOL_RATE"]], "harsh_brake_rate": row[E["HARSH_RATE"]],
-            "num_vehicles": row[E["NUM_VEH"]], "len_ego_route": row[E["LEN_ROUTE_M"]]}
-
-
-def info_of(ep, t):
-    """cbev_step's per-step float32 export (include/cbev.h) from the fixture."""
-    M = ep._fx.meta
-    o = np.zeros(16, np.float64)
-    o[0:7], o[7:11] = ep.comfort[t], ep.control[t]
-    o[11], o[12] = ep.reward[t], ep.dist2wp[t]
-    o[13], o[14], o[15] = ep.tile[t], LY.COLL[M["coll_names"][int(ep.collided[t])]], ep.n_actors_state[t]
-    return o.astype(np.float32)
-
-
 @pytest.mark.parametrize("config,split", RUNS, ids=[f"{c}-{'default' if s is None else 'split' + str(s)}" for c, s in RUNS])
 def test_device_replays_the_reference_episodes(config, split):
-    fx = EF.load()
-    eps = fx.of_config(config)
+    eps = EF.load().of_config(config)
     n = len(eps)
     assert n >= 1
-    P, padded = world_of(eps[0].config)
-    caps = CAPS_FULL
-    layout = LY.Layout.make(caps)
-    recs = np.zeros((n, layout.record_bytes), np.uint8)
-    for e, ep in enumerate(eps):
-        need = ep.scene_spec().caps_needed()
-        assert all(a <= b for a, b in zip(need, (caps.route_cap, caps.actor_cap, caps.actor_route_cap, caps.tl_cap))), need
-        recs[e], _, _ = pack_episode(ep, caps)
-    L = lib()
-    dw = DevWorld(P, padded, caps)
-    if split is not None:
-        check(L.cbev_set_split_step(dw.ctx, split), "split_step")
-    S = P.size
-    d_recs = torch.from_numpy(recs).cuda()
-    frames = torch.zeros((n, S, S), dtype=torch.uint8, device="cuda")
-    check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(frames), 1, None), "reset")
-    stats = EpisodeStatsOn(dw.ctx, n)
-    torch.cuda.synchronize()
-    dev = Deviation(libm=LIBM, actor_yaw_mod=True)
-    h = d_recs.cpu().numpy()
-    for e, ep in enumerate(eps):
-        v = LY.RecordView(h[e], layout)
-        compare_reset(ep, v, dev, None)
-    rew, term, trunc, cause, info = out_bufs(n).values()
-    cont = P.action_kind == 1
-    compared = rows_seen = 0
-    for t in range(max(ep.n_steps for ep in eps)):
-        live = [e for e, ep in enumerate(eps) if t < ep.n_steps]
-        acts = np.zeros((n, 3), np.float32) if cont else np.zeros(n, np.int32)  # finished envs: nothing pressed
-        for e in live:
-            acts[e] = eps[e].action(t)
-        a = torch.from_numpy(acts).cuda()
-        check(L.cbev_step(dw.ctx, ptr(d_recs), n, ptr(a), ptr(frames), ptr(rew), ptr(term), ptr(trunc), ptr(cause),
-                          ptr(info), None), "step")
-        torch.cuda.synchronize()
-        h = d_recs.cpu().numpy()
-        h_rew, h_term, h_trunc = rew.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy()
-        h_cause, h_info = cause.cpu().numpy(), info.cpu().numpy()
-        slot = t % stats.RING
-        rows = stats.rows[slot, :int(stats.counts[slot].item())].cpu().numpy()
-        by_env = {int(r[LY.EP["ENV"]]): r for r in rows}
-        for e in live:
-            ep, tag = eps[e], (eps[e].name, t)
-            compare_step(ep, t, LY.RecordView(h[e], layout), int(h_cause[e]), dev)
-            dev.check("reward", [h_rew[e]], [ep.reward[t]], tag + ("reward output",))
-            assert h_term[e] == ep.terminated[t] and h_trunc[e] == ep.truncated[t], tag + ("term, trunc outputs",)
-            want = info_of(ep, t)
-            assert np.array_equal(h_info[e, 13:], want[13:]), tag + ("info ints", h_info[e, 13:], want[13:])
-            assert np.all(np.abs(h_info[e, :13].astype(np.float64) - want[:13]) <=
-                          BOUND["reward"][0] + LIBM + F32_ULP * np.abs(want[:13])), tag + ("info", h_info[e], want)
-            if ep.terminated[t]:
-                assert e in by_env, tag + ("no summary row at the terminal step",)
-                row = by_env[e]
-                assert row[LY.EP["EPISODE"]] == 0, tag
-                compare_summary(ep, summary_of_row(row), int(row[LY.EP["CAUSE"]]), dev)
-                rows_seen += 1
-            else:
-                assert e not in by_env, tag + ("a summary row before the terminal step",)
-            compared += 1
-    assert compared == sum(ep.n_steps for ep in eps) and rows_seen == n
-    assert error_flags(dw.ctx) == 0
+    compared, dev = replay_on_device(eps, split, ends=True)
     print(f"\n{config}: {n} envs, {compared} env-steps, largest deviations (abs, rel):",
           {k: (f"{x:.3e}", f"{r:.3e}") for k, (x, r) in dev.seen.items()})
