@@ -10,6 +10,7 @@ long as its tensors are used.
 from __future__ import annotations
 
 import ctypes
+from fractions import Fraction
 from typing import NamedTuple
 
 import numpy as np
@@ -17,6 +18,7 @@ import torch
 
 from carlabev_env_amd import layout as LY
 from carlabev_env_amd._lib import check, lib
+from stats_ref import STATS_DTYPE, WindowModel
 
 P_ = ctypes.c_void_p
 KEYS = ("rew", "term", "trunc", "cause", "info")
@@ -44,12 +46,61 @@ class DevWorld:
         lib().cbev_destroy(self.ctx)
 
 
+# ---------------------------------------------------------------------- episode summary rows
+# (record accumulator, row column) of the per-episode means: accumulator / length
+EP_MEANS = (("EP_SPEED", "MEAN_SPEED"), ("EP_ABS_AL", "MEAN_ABS_AL"), ("EP_ABS_ALAT", "MEAN_ABS_ALAT"),
+            ("EP_ABS_JL", "MEAN_ABS_JL"), ("EP_ABS_JLAT", "MEAN_ABS_JLAT"), ("EP_ABS_YR", "MEAN_ABS_YR"),
+            ("EP_ABS_YACC", "MEAN_ABS_YACC"), ("EP_VIOL", "VIOL_RATE"), ("EP_HARSH", "HARSH_RATE"))
+# columns summed over the episode's steps in another order than the expectation's: within 1e-9
+CLOSE_COLUMNS = ("RETURN",) + tuple(c for _, c in EP_MEANS)
+ROW_COLUMNS = tuple(c for c in LY.EP if c != "SECONDS")  # every column but the elapsed time
+
+
+def check_summary_row(row, want, bound, tag, exact=()):
+    """One summary row (float64[len(LY.EP)]) against `want`, {column: value} of the
+    columns to compare: CLOSE_COLUMNS within rtol 1e-9 (atol 1e-12) unless named
+    in `exact`, MEAN_REWARD within `bound` of an exact mean (both as Fractions),
+    every other column equal. Raises an AssertionError that names the column. A
+    pure function."""
+    for col, w in want.items():
+        g = row[LY.EP[col]]
+        if col == "MEAN_REWARD":
+            ok = abs(Fraction(float(g)) - Fraction(w)) <= bound
+        elif col in CLOSE_COLUMNS and col not in exact:
+            ok = bool(np.isclose(g, w, rtol=1e-9, atol=1e-12))
+        else:
+            ok = bool(g == w)
+        assert ok, (tag, col, float(g), float(w))
+
+
+def window_columns(model, episode=None):
+    """The columns of a termination's row that a WindowModel gives, before the push."""
+    s = model.summary()
+    return {"EPISODE": model.episode if episode is None else episode, "MEAN_REWARD": s["mean_reward"],
+            "SUCCESS_RATE": s["success_rate"], "COLLISION_RATE": s["collision_rate"],
+            "UNFINISHED_RATE": s["unfinished_rate"]}
+
+
+def episode_columns(env, view):
+    """The columns of a termination's row that a record at its terminal step gives
+    (an oracle's RecordView): the per-episode means as accumulator / length."""
+    ln = max(view.i("EP_LEN"), 1)
+    want = {"ENV": env, "CAUSE": view.i("CAUSE"), "RETURN": view.h("EP_RETURN"), "LENGTH": view.i("EP_LEN"),
+            "MEAN_TTC": 0.0, "MEAN_PROGRESS": 0.0, "NUM_VEH": view.h("NUM_VEH"), "LEN_ROUTE_M": view.h("LEN_ROUTE_M"),
+            "CTX_ID": view.i("CTX_ID")}
+    want.update({col: view.h(acc) / ln for acc, col in EP_MEANS})
+    return want
+
+
 class EpisodeStatsOn:
     """The device episode statistics (cbev_set_episode_stats) on a context, as
     the bench's info_mode "full" runs the step: k_ego then updates the per-env
     Stats accumulators and writes a summary row per termination (the kernel
     variant the headline measures). `check(step, term, sample, views, causes)`
-    compares this step's rows with the oracle's records of the sampled envs."""
+    compares this step's rows with the oracle's records of the sampled envs in
+    every column but SECONDS; the window columns come from a WindowModel per
+    sampled env, so an env that is sampled once is sampled at each of its
+    terminations."""
     RING = 4
 
     def __init__(self, ctx, n):
@@ -60,15 +111,25 @@ class EpisodeStatsOn:
         check(lib().cbev_set_episode_stats(ctx, ptr(self.stats), n, ptr(self.rows), ptr(self.counts), self.RING),
               "episode_stats")
         self.episodes = np.zeros(n, np.int64)
+        self.windows = {}
         self.rows_seen = 0
 
-    def check(self, step, term_all, sample, views, causes):
+    def step_rows(self, step):
+        """{env: row} of the rows `step` wrote, one per env, and their count."""
         slot = step % self.RING
         cnt = int(self.counts[slot].item())
-        assert cnt == int(term_all.sum()), (step, cnt, int(term_all.sum()))
-        rows = self.rows[slot, :cnt].cpu().numpy()
+        rows = self.rows[slot, :min(cnt, self.n)].cpu().numpy()
         by_env = {int(r[LY.EP["ENV"]]): r for r in rows}
         assert len(by_env) == cnt, (step, "one row per terminated env")
+        return by_env, cnt
+
+    def structs(self):
+        """The per-env cbev_episode_stats as a STATS_DTYPE array (a host copy)."""
+        return self.stats.cpu().numpy().view(STATS_DTYPE)[:, 0]
+
+    def check(self, step, term_all, sample, views, causes):
+        by_env, cnt = self.step_rows(step)
+        assert cnt == int(term_all.sum()), (step, cnt, int(term_all.sum()))
         for j, e in enumerate(sample):
             v = views[j]
             if not v.i("TERM"):
@@ -76,11 +137,12 @@ class EpisodeStatsOn:
                 continue
             r = by_env[int(e)]
             assert r[LY.EP["CAUSE"]] == causes[j] == v.i("CAUSE"), (step, e)
-            assert r[LY.EP["EPISODE"]] == self.episodes[e], (step, e)
-            assert r[LY.EP["LENGTH"]] == v.i("EP_LEN"), (step, e)
-            assert np.isclose(r[LY.EP["RETURN"]], v.h("EP_RETURN"), rtol=1e-9, atol=1e-12), (step, e)
-            ln = max(v.i("EP_LEN"), 1)
-            assert np.isclose(r[LY.EP["MEAN_SPEED"]], v.h("EP_SPEED") / ln, rtol=1e-9, atol=1e-12), (step, e)
+            m = self.windows.setdefault(int(e), WindowModel())
+            assert m.episode == self.episodes[e], (step, e, "a termination of a sampled env was not sampled")
+            want = {**episode_columns(int(e), v), **window_columns(m, self.episodes[e])}
+            assert set(want) == set(ROW_COLUMNS)
+            check_summary_row(r, want, m.mean_bound(), (step, int(e)))
+            m.push(r[LY.EP["RETURN"]], int(r[LY.EP["CAUSE"]]))
             self.rows_seen += 1
         for e in np.flatnonzero(term_all):
             self.episodes[e] += 1
@@ -113,11 +175,14 @@ class Lane(NamedTuple):
     out: dict
 
 
-def make_lane(P, padded, caps, recs, bank, F, *, split=None, deferred=None, preview=None, stats=True):
+def make_lane(P, padded, caps, recs, bank, F, *, split=None, deferred=None, preview=None, stats=True,
+              stats_first=False):
     """A context on host records `recs` and bank rows `bank` (None: no bank), reset
     into an F-slot ring. split / preview / deferred: cbev_set_split_step,
     cbev_set_reset_preview, cbev_set_deferred_reset; one left None is not set, so
-    the context keeps the library's default. stats: the episode statistics on."""
+    the context keeps the library's default. stats: the episode statistics on;
+    stats_first: turned on before cbev_reset, which then stamps the first
+    episode's start (otherwise t0 stays the 0 the buffer was allocated with)."""
     L = lib()
     S, n = P.size, len(recs)
     dw = DevWorld(P, padded, caps)
@@ -134,16 +199,17 @@ def make_lane(P, padded, caps, recs, bank, F, *, split=None, deferred=None, prev
         check(L.cbev_bank_frames(dw.ctx, ptr(d_bank), len(bank), ptr(bf), None), "bank_frames")
     d_recs = torch.from_numpy(recs.copy()).cuda()
     ring = torch.zeros((F, n, S, S), dtype=torch.uint8, device="cuda")
+    st = EpisodeStatsOn(dw.ctx, n) if stats and stats_first else None
     check(L.cbev_reset(dw.ctx, ptr(d_recs), n, None, 0, None, None, 0, ptr(ring), F, None), "reset")
     out = out_bufs(n)
     if stats:
-        out["stats"] = EpisodeStatsOn(dw.ctx, n)
+        out["stats"] = st if stats_first else EpisodeStatsOn(dw.ctx, n)
     return Lane(dw, d_bank, bf, d_recs, ring, out)
 
 
-def make_lanes(P, padded, caps, recs, bank, F, modes, stats=True):
+def make_lanes(P, padded, caps, recs, bank, F, modes, stats=True, stats_first=False):
     """One lane per mode (a dict of make_lane's toggles) on the same records and bank."""
-    return [make_lane(P, padded, caps, recs, bank, F, stats=stats, **mode) for mode in modes]
+    return [make_lane(P, padded, caps, recs, bank, F, stats=stats, stats_first=stats_first, **mode) for mode in modes]
 
 
 def step_all(lanes, acts_t, t):

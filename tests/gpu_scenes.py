@@ -7,6 +7,7 @@ here touches the GPU or the library at import.
 from __future__ import annotations
 
 import dataclasses
+from functools import lru_cache
 
 import numpy as np
 import torch
@@ -445,6 +446,78 @@ def primed_case(extra_off=()):
 def preview_delta(lanes, base):
     hcount, fcount = preview_counts(lanes[1])
     return hcount - base[0], fcount - base[1]
+
+
+# ---------------------------------------------------------------------- a bank of episodes that end at once
+STATS_CAUSES = ("collision", "success", "out_of_bounds", "max_actions", "off_road")
+# (cause, steps the episode lasts) of the rows one pass of stats_bank adds
+STATS_ROW_KINDS = (("collision", 1), ("success", 1), ("success", 2), ("success", 3), ("out_of_bounds", 1),
+                   ("max_actions", 1), ("max_actions", 2), ("max_actions", 3), ("off_road", 1))
+STATS_ACTION = 1  # gas, every env on every step
+
+
+def _class_dy(classes, x, y, cls):
+    """The nearest row offset at which the hero's next few steps along the road (a
+    5 x 14 block of texels ahead of x) lie in class cls."""
+    xx = int(round(x))
+    for d in range(1, 60):
+        for dy in (-d, d):
+            yy = int(round(y)) + dy
+            if yy >= 2 and (classes[yy - 2:yy + 3, xx - 2:xx + 12] == cls).all():
+                return float(dy)
+    raise AssertionError(f"no block of class {cls} within 60 texels of the road")
+
+
+@lru_cache(maxsize=None)
+def stats_bank(max_life=3, presets=False, passes=2):
+    """Ego-only records (CAPS_LONG2: the canonical reset folds into the step) under
+    the shaping reward, the one profile that reaches all five terminal causes,
+    each ending after 1 to max_life steps of STATS_ACTION: the hero on a class-0
+    texel (collision), 1 to 3 steps short of the goal (success), 70 texels beside
+    its route (out_of_bounds), KSTEPS 1 to 3 short of max_actions (max_actions,
+    the truncation, which no rate counts), and on the sidewalk with OFFROAD one
+    short of offroad_terminate_after (off_road). presets: every third row starts
+    with EP_RETURN at about +-1e9 instead of 0, which a bank row is free to do,
+    so an episode of one step can bring a large return into the window.
+    CTX_ID is 100 + b and NUM_VEH b % 5, so a row's scene columns tell the rows apart.
+    Returns (P, padded, bank, layout, table); table[b] = (steps to the end, cause,
+    return) of row b, as the CPU oracle runs it."""
+    P, padded, classes = EC.authored_world(128, reward_profile="shaping_base_v1")
+    kinds = [k for _ in range(passes) for k in STATS_ROW_KINDS if k[1] <= max_life]
+    lengths = (65, 127, 128, 64, 33)
+    specs = [dataclasses.replace(EC.long_route_spec(lengths[b % len(lengths)], 128, seed=700 + b), vehicles=[],
+                                 pedestrians=[]) for b in range(len(kinds))]
+    bank, layout, views = EC.pack_records(specs, 128, CAPS_LONG2)
+    rng = np.random.default_rng(77)
+    for b, (v, (kind, life)) in enumerate(zip(views, kinds)):
+        nr = v.i("NROUTE")
+        i = nr - 2 - life if kind == "success" else 11 + b % 5
+        EC.set_pose(v, v.cx[i], v.cy[i], v.cyaw[i], 30.0)
+        v.hi[LY.HI["TIDX"]] = i
+        if kind == "collision":
+            v.hd[LY.HD["Y"]] += _class_dy(classes, v.cx[i], v.cy[i], 0)
+        elif kind == "out_of_bounds":
+            v.hd[LY.HD["Y"]] += 70.0
+        elif kind == "max_actions":
+            v.hi[LY.HI["KSTEPS"]] = P.max_actions - life
+        elif kind == "off_road":
+            v.hd[LY.HD["Y"]] += _class_dy(classes, v.cx[i], v.cy[i], 2)
+            v.hi[LY.HI["OFFROAD"]] = P.offroad_terminate_after - 1
+        v.hi[LY.HI["CTX_ID"]], v.hd[LY.HD["NUM_VEH"]] = 100 + b, float(b % 5)  # what a summary row reports of its scene
+        if presets and b % 3 == 1:
+            v.hd[LY.HD["EP_RETURN"]] = (-1.0) ** (b // 3) * 1e9 * rng.uniform(0.5, 1.0)
+    orc = O.Oracle(P, padded, CAPS_LONG2.c(), layout.record_bytes)
+    table = []
+    for b, (kind, life) in enumerate(kinds):
+        r, act = bank[b].copy(), np.array(STATS_ACTION, np.int32)
+        for t in range(1, life + 1):
+            orc.step_one(r, act, None)
+            v = LY.RecordView(r, layout)
+            assert bool(v.i("TERM")) == (t == life), (b, kind, life, t, v.i("CAUSE"))
+        assert v.i("CAUSE") == LY.CAUSE[kind], (b, kind, LY.CAUSE_NAME[v.i("CAUSE")])
+        table.append((life, LY.CAUSE[kind], float(v.h("EP_RETURN"))))
+    bank.setflags(write=False)
+    return P, padded, bank, layout, tuple(table)
 
 
 # ---------------------------------------------------------------------- the evaluation envs

@@ -9,9 +9,14 @@ comfort metrics of `hero.last_comfort`.
 """
 from __future__ import annotations
 
+import math
+import re
 from collections import deque
+from fractions import Fraction
 
 import numpy as np
+
+from carlabev_env_amd import layout as LY
 
 COMFORT_KEYS = ("accel_long", "accel_lat", "jerk_long", "jerk_lat", "yaw_rate", "yaw_acc")
 BOUNDS = {"accel_long": 2.0, "accel_lat": 2.0, "yaw_rate": 20.0, "jerk_long": 3.0, "jerk_lat": 3.0, "yaw_acc": 120.0}
@@ -44,6 +49,23 @@ class EpisodeStats:  # stats.py:19-84
         return float(np.mean(vals)) if vals else 0.0
 
 
+def episode_summary(c: EpisodeStats) -> dict:
+    """The entries of get_episode_info (stats.py:127-148) that depend on the
+    finished episode alone, not on the window."""
+    return {
+        "termination": c.cause, "return": c.episode_return, "length": len(c.rewards),
+        "mean_speed": c.mean(c.speeds), "mean_ttc": c.mean(c.ttc), "mean_progress": c.mean(c.progress),
+        "mean_abs_accel_long": c.mean(c.comfort_values["accel_long"]),
+        "mean_abs_accel_lat": c.mean(c.comfort_values["accel_lat"]),
+        "mean_abs_jerk_long": c.mean(c.comfort_values["jerk_long"]),
+        "mean_abs_jerk_lat": c.mean(c.comfort_values["jerk_lat"]),
+        "mean_abs_yaw_rate": c.mean(c.comfort_values["yaw_rate"]),
+        "mean_abs_yaw_acc": c.mean(c.comfort_values["yaw_acc"]),
+        "comfort_violation_rate": c.mean(c.comfort_step_violations),
+        "harsh_brake_rate": c.mean(c.harsh_brake_flags),
+    }
+
+
 class Stats:  # stats.py:87-148
     def __init__(self, maxlen=200):
         self.current = EpisodeStats()
@@ -61,21 +83,127 @@ class Stats:  # stats.py:87-148
         c = self.current
         vals = [ep.episode_return for ep in self.history]
         summary = {
-            "episode": self.episode, "termination": c.cause, "return": c.episode_return, "length": len(c.rewards),
+            "episode": self.episode,
             "mean_reward": np.mean(vals) if vals else 0.0,
             "success_rate": self._count("success"), "collision_rate": self._count("collision"),
             "unfinished_rate": self._count("off_road"),
-            "mean_speed": c.mean(c.speeds), "mean_ttc": c.mean(c.ttc), "mean_progress": c.mean(c.progress),
-            "mean_abs_accel_long": c.mean(c.comfort_values["accel_long"]),
-            "mean_abs_accel_lat": c.mean(c.comfort_values["accel_lat"]),
-            "mean_abs_jerk_long": c.mean(c.comfort_values["jerk_long"]),
-            "mean_abs_jerk_lat": c.mean(c.comfort_values["jerk_lat"]),
-            "mean_abs_yaw_rate": c.mean(c.comfort_values["yaw_rate"]),
-            "mean_abs_yaw_acc": c.mean(c.comfort_values["yaw_acc"]),
-            "comfort_violation_rate": c.mean(c.comfort_step_violations),
-            "harsh_brake_rate": c.mean(c.harsh_brake_flags),
+            **episode_summary(c),
         }
         self.history.append(self.current)
         self.episode += 1
         self.reset()
         return summary
+
+
+# ---------------------------------------------------------------------- the device's window, as exact arithmetic
+# cbev_episode_stats (include/cbev_layout.h): the state of Stats that outlives an
+# episode, one struct per env in a caller-owned buffer
+STATS_HIST = int(re.search(r"#define CBEV_STATS_HIST (\d+)", open(LY.HEADER).read()).group(1))
+STATS_DTYPE = np.dtype([("ret", "<f8", (STATS_HIST,)), ("sum_hi", "<f8"), ("sum_lo", "<f8"), ("t0", "<f8"),
+                        ("n", "<i4"), ("head", "<i4"), ("episode", "<i4"),
+                        ("n_success", "<i4"), ("n_collision", "<i4"), ("n_offroad", "<i4"),
+                        ("cause", "u1", (STATS_HIST,)), ("pad", "u1", (8,))])
+# the struct's counter of each cause a rate counts (d_stats_count); no rate counts the other causes
+COUNTERS = {"n_success": LY.CAUSE["success"], "n_collision": LY.CAUSE["collision"], "n_offroad": LY.CAUSE["off_road"]}
+RATES = {"success_rate": "n_success", "collision_rate": "n_collision", "unfinished_rate": "n_offroad"}
+TERMINAL_CAUSES = tuple(LY.CAUSE[k] for k in ("collision", "success", "out_of_bounds", "max_actions", "off_road"))
+DD_EPS = 2.0 ** -100  # relative error of the double-double window sum the device claims (cbev.hip, d_dd_add)
+
+
+def mean_bound(exact_mean, n, max_abs) -> Fraction:
+    """How far MEAN_REWARD may be from the exact mean of a window of n returns of
+    magnitude at most max_abs. The device computes fl(fl(hi + lo) / n): two
+    roundings of at most half an ulp each, one more ulp for a binade crossed on
+    the way, and the double-double sum's own error n * max_abs * 2^-100."""
+    return 2 * Fraction(math.ulp(float(exact_mean))) + Fraction(n) * Fraction(max_abs) * Fraction(DD_EPS)
+
+
+class WindowModel:
+    """deque(maxlen=200) of (return, cause) with the episode count and the ring's
+    next slot: what a cbev_episode_stats holds, with nothing rounded."""
+
+    def __init__(self, entries=(), episode=None, head=None):
+        self.window = deque(((float(r), int(c)) for r, c in entries), maxlen=STATS_HIST)
+        self.episode = len(self.window) if episode is None else int(episode)
+        self.head = len(self.window) % STATS_HIST if head is None else int(head)
+        self.evicted = []  # (return, cause) of every entry push() dropped, oldest first
+
+    def __len__(self):
+        return len(self.window)
+
+    def exact_sum(self) -> Fraction:
+        return sum((Fraction(r) for r, _ in self.window), Fraction(0))
+
+    def max_abs(self) -> float:
+        return max((abs(r) for r, _ in self.window), default=0.0)
+
+    def count(self, cause) -> int:
+        return sum(1 for _, c in self.window if c == cause)
+
+    def summary(self) -> dict:
+        """The four window columns of a termination's row: over the window before
+        the current episode enters it. mean_reward is exact; a rate is the one
+        float64 division the device does."""
+        n = len(self.window)
+        out = {"mean_reward": self.exact_sum() / n if n else Fraction(0)}
+        for rate, counter in RATES.items():
+            out[rate] = float(self.count(COUNTERS[counter])) / n if n else 0.0
+        return out
+
+    def mean_bound(self) -> Fraction:
+        return mean_bound(self.summary()["mean_reward"], len(self.window), self.max_abs())
+
+    def push(self, ret, cause):
+        if len(self.window) == STATS_HIST:
+            self.evicted.append(self.window[0])
+        self.window.append((float(ret), int(cause)))
+        self.head = (self.head + 1) % STATS_HIST
+        self.episode += 1
+
+    def to_struct(self, head=None, t0=0.0) -> np.ndarray:
+        """One STATS_DTYPE record of this window with the ring's next slot at
+        `head` (the model keeps it): entry i, oldest first, in slot
+        (head - n + i) % 200, so the slot a full ring evicts next holds the
+        oldest; unused slots zero; the sum as the normalised double-double of
+        the exact one."""
+        if head is not None:
+            self.head = int(head)
+        rec = np.zeros((), STATS_DTYPE)
+        n = len(self.window)
+        for i, (r, c) in enumerate(self.window):
+            rec["ret"][(self.head - n + i) % STATS_HIST] = r
+            rec["cause"][(self.head - n + i) % STATS_HIST] = c
+        s = self.exact_sum()
+        rec["sum_hi"] = float(s)
+        rec["sum_lo"] = float(s - Fraction(float(s)))
+        rec["t0"] = t0
+        rec["n"], rec["head"], rec["episode"] = n, self.head, self.episode
+        for counter, cause in COUNTERS.items():
+            rec[counter] = self.count(cause)
+        return rec
+
+    def check_struct(self, rec, tag=None):
+        """A record read back from the device against this window: the rings'
+        bytes, n, head, episode and the three counters exact; the double-double
+        within n * max|ret| * 2^-100 of the exact sum, and normalised."""
+        want = self.to_struct()
+        for k in ("ret", "cause"):
+            assert rec[k].tobytes() == want[k].tobytes(), (tag, k, np.flatnonzero(rec[k] != want[k])[:8].tolist())
+        for k in ("n", "head", "episode", *COUNTERS):
+            assert int(rec[k]) == int(want[k]), (tag, k, int(rec[k]), int(want[k]))
+        hi, lo = float(rec["sum_hi"]), float(rec["sum_lo"])
+        err = abs(Fraction(hi) + Fraction(lo) - self.exact_sum())
+        bound = Fraction(len(self.window)) * Fraction(self.max_abs()) * Fraction(DD_EPS)
+        assert err <= bound, (tag, "sum", hi, lo, float(err), float(bound))
+        assert hi == hi + lo, (tag, "the double-double is not normalised", hi, lo)
+
+
+def dd_add(hi, lo, x):
+    """d_dd_add (cbev.hip) in Python floats, which are IEEE binary64 like the
+    device's: (hi, lo) += x with TwoSum."""
+    s = hi + x
+    bp = s - hi
+    err = (hi - (s - bp)) + (x - bp)
+    t = lo + err
+    hi = s + t
+    return hi, t - (hi - s)
